@@ -25,6 +25,7 @@ hipGraph SEGMENTS with the collectives issued by the host between them (models/s
   f32          -- (N=1) the exact-fp32 datapath, the reference's own arithmetic, on the same workload, timed the same way.
   cpu_baseline -- the CPU oracle (a torch-CPU restatement of the reference step, kind "port") timed on this host's
                   cores on a bounded sample (one sequence), rank 0 at N=1 only.
+  dump_outputs -- (--dump-outputs DIR) what was written there: see dump_outputs().
 """
 import argparse
 import json
@@ -137,6 +138,40 @@ def cpu_baseline(seconds_budget=30.0):
             'sample': '%d full train step(s) of 1 sequence (B=1, T=%d, 64x64x3, fp32 torch-CPU oracle), %.1f s' % (nsteps, SEQ, el)}
 
 
+DUMP_SAMPLE = 1 << 22    # elements of the variables written to variables_sample.npy by --dump-outputs (16 MB as float32)
+
+
+def dump_outputs(out_dir, engine, info):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST timed step, as DIR/<name>.npy, for comparing two builds
+    output for output (same arguments -> same inputs: images, variables and per-step noise are all seeded).  train_step returns the
+    step's losses and updates the variables in place, so the files are
+      d_loss, g_loss, loss_<term>   the losses of the step (float32 scalars; one loss_* file per weighted term of d_losses / g_losses)
+      variable_sums                 float64 sum of every variable after the step, in variable-table order (every element counts)
+      variables_sample              float32, DUMP_SAMPLE elements of all variables concatenated in that order, at the sorted
+                                    positions rng(0).choice(total, DUMP_SAMPLE, replace=False) picks (the whole set is ~70 MB)
+    Returns a description for the bench line."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {'d_loss': info['d_loss'], 'g_loss': info['g_loss']}
+    for group in ('d_losses', 'g_losses'):
+        for term, (val, _) in info[group].items():
+            arrays['loss_' + term] = val
+    arrays = {k: np.asarray(torch.as_tensor(v).detach().float().cpu().numpy(), dtype=np.float32) for k, v in arrays.items()}
+    store = engine.store
+    names = list(store.specs)
+    flat = torch.cat([store[n].detach().reshape(-1).float() for n in names]).cpu().numpy()
+    sizes = [store[n].numel() for n in names]
+    bounds = np.cumsum([0] + sizes)
+    arrays['variable_sums'] = np.array([flat[bounds[i]:bounds[i + 1]].sum(dtype=np.float64) for i in range(len(names))], dtype=np.float64)
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, size=min(DUMP_SAMPLE, flat.size), replace=False))
+    arrays['variables_sample'] = flat[idx]
+    nbytes = 0
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
+        nbytes += v.nbytes
+    return {'dir': out_dir, 'files': sorted(k + '.npy' for k in arrays), 'bytes': nbytes, 'variables': len(names), 'variable_elements': int(flat.size)}
+
+
 def pin_rank(local_rank, local_world):
     """One process per GPU: give rank r the r-th contiguous slice of the cores this job may use (sched_setaffinity) and size torch's
     host thread pool to it.  Eight Python interpreters that each issue ~2.5 k launches (or 8 graph segments + 7 collectives) per step
@@ -180,7 +215,11 @@ def main():
     ap.add_argument('--retune', action='store_true', help='ignore the shipped tuning table and time every conv problem again')
     ap.add_argument('--save-tuning', default=None, help='write the tuning table found during this run to this path')
     ap.add_argument('--dry-run', action='store_true', help='print the launch plan (launcher command line, per-rank core binding, workload) as JSON and exit; needs no GPU')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (losses, updated variables) to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
 
     if args.dry_run:
         cpus = sorted(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else []
@@ -287,6 +326,7 @@ def main():
     # ConvLSTM gate-conv launches and around whole cells -- instrumentation never sits inside the timed region.
     engine.use_graph = engine.use_graph and not args.eager     # the engine's own choice stands (eager under a host-blocking backend)
     dt, info = timed_steps(engine, args.warmup, args.steps)
+    dumped = dump_outputs(args.dump_outputs, engine, info) if (args.dump_outputs and rank == 0) else None   # before any further step
     mode = 'eager launches'
     if engine.use_graph and engine.graph is not None:
         nseg = engine.graph.segments
@@ -534,6 +574,8 @@ def main():
                                     'side_stream': engine.replicas.comm_stream is not None, 'binding': binding,
                                     'collectives_in_graph': bool(getattr(engine, 'graph_collectives', False)),
                                     'ranks_seen_by_backend': dist.get_world_size(), 'allreduce_bytes_per_step': 4 * st['elements'] // max(1, args.warmup + args.steps + INST_STEPS)}
+    if dumped is not None:
+        result['dump_outputs'] = dumped
     if dist is not None and os.environ.get('SAVP_BENCH_CHECK_REPLICAS', '0') == '1':
         result['replicas_identical'] = bool(engine.replicas.checksum_identical())      # collective: every rank calls it
     if rank == 0 and args.save_tuning:

@@ -2,7 +2,6 @@
 step-frequency rules, side files) -- CPU only; the GPU smoke of the runners is tests/test_gpu_model.py::test_train_and_generate_scripts."""
 import json
 import os
-import re
 import struct
 import zlib
 
@@ -12,22 +11,22 @@ import pytest
 from scripts import generate as G
 from scripts import train as T
 
-REF = '/root/reference/scripts'
+# the flags the reference's scripts/train.py and scripts/generate.py declare (tests/golden/make_reference_fixtures.py)
+REF_FLAGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_script_flags.json')
 
 
-def _ref_flags(path):
-    src = open(path).read()
-    return set(re.findall(r'add_argument\(\s*"(--[a-z_]+)"', src))
+def _ref_flags(name):
+    with open(REF_FLAGS) as fh:
+        return set(json.load(fh)[name])
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason='reference not mounted')
 def test_flags_match_the_reference_scripts():
     ours = {a.option_strings[0] for a in T.build_parser()._actions if a.option_strings and a.option_strings[0] != '-h'}
-    assert _ref_flags(os.path.join(REF, 'train.py')) <= ours, _ref_flags(os.path.join(REF, 'train.py')) - ours
-    assert ours - _ref_flags(os.path.join(REF, 'train.py')) == {'--synthetic_shape'}
+    assert _ref_flags('train.py') <= ours, _ref_flags('train.py') - ours
+    assert ours - _ref_flags('train.py') == {'--synthetic_shape'}
     ours = {a.option_strings[0] for a in G.build_parser()._actions if a.option_strings and a.option_strings[0] != '-h'}
-    assert _ref_flags(os.path.join(REF, 'generate.py')) <= ours
-    assert ours - _ref_flags(os.path.join(REF, 'generate.py')) == {'--synthetic_shape'}
+    assert _ref_flags('generate.py') <= ours
+    assert ours - _ref_flags('generate.py') == {'--synthetic_shape'}
 
 
 def test_flag_defaults():
