@@ -2,7 +2,9 @@
 
 Used by tests/test_gpu_*.py (pytest -m gpu), by __graft_entry__.smoke() and by tests/tools/run_gpu_checks.py (which
 dumps every result to gpurun_out/ instead of stopping at the first failure).  Each check returns a list of
-(name, err, tol) tuples; err is max|hip - oracle| / max(|oracle|) with the oracle evaluated in float64.
+(name, err, tol) tuples; err is max|hip - oracle| / max(|oracle|) with the oracle evaluated in float64.  The bf16 datapath's `_exact`
+rows evaluate the oracle on the bf16-rounded operands the kernel multiplies; their bf16-destination rows are element counts and
+fractions (tests/bf16_exact.py).
 """
 import ctypes
 
@@ -12,18 +14,12 @@ import torch
 from oracle import ops as O
 from oracle import savp as OS
 from oracle import tf_ops as TF
+from tests.bf16_exact import TOL_EXACT, bf16_apart, bracket_rows, rel_err, rne, wgrad_tol, window
 from video_prediction_amd import kernels as K
 from video_prediction_amd import lib
 
 DEV = 'cuda:0'
 TOL_OP = 2e-5          # fp32 per-op tolerance: rel <= 2e-5 vs the fp64 oracle
-
-
-def rel_err(got, ref):
-    got = got.detach().double().cpu()
-    ref = ref.detach().double().cpu()
-    denom = max(ref.abs().max().item(), 1e-30)
-    return (got - ref).abs().max().item() / denom
 
 
 def dev(t):
@@ -120,7 +116,32 @@ def patch_lds_bytes(cred, kh, kw, wm, wn, nw=4, sh=1, sw=1, dgrad=False, hm=64):
     return ni * ph * pitch * 2 + 2 * 64 * wn * (nks * 16 + 8) * 2
 
 
+def _conv_grads(x, w, b, dy, k, s, p, pa):
+    """fp64 y = conv(x, w) + b and the data / weight gradients of <y, dy> (CPU autograd)."""
+    x = x.detach().clone().requires_grad_(True)
+    w = w.detach().clone().requires_grad_(True)
+    y = _ref_conv(x, w, k, s, p, pa) + b.detach()
+    (y * dy.detach()).sum().backward()
+    return y.detach(), x.grad, w.grad
+
+
+def wgrad_rounds_operands(a):
+    """Whether a bf16-precision weight gradient (filled SavpConvArgs `a`) multiplies bf16-rounded x / dy.  The LDS-patch kernel
+    (conv_wgrad_patch.hip, conv_wgrad_patch_try), the RGB-side kernel (conv_thin.hip, taken under tile 0) and the generic kernel's bf16
+    variant (conv_igemm.hip, wgrad_generic_plan: g.wbf16 = bf16 && va && vb) do; with Cx or Cy not a multiple of 4 (or rows not in
+    float4 steps) the generic kernel runs in exact fp32 by design, and the exact reference keeps the fp32 operands there."""
+    if a.src_bf16 or a.out_bf16:
+        return True
+    K._conv_scratch(a, torch.device(DEV))          # the RGB-side kernel takes the call only with its scratch at hand, as K.conv gives it
+    if ((a.tile >> 8) & 3) == 0 and lib.get().savp_conv_special(ctypes.byref(a)):
+        return True
+    strides = (a.x_sn, a.x_sd, a.x_sh, a.x_sw, a.y_sn, a.y_sd, a.y_sh, a.y_sw)
+    return a.Cx % 4 == 0 and a.Cy % 4 == 0 and all(int(v) % 4 == 0 for v in strides)
+
+
 def check_conv(cases=None, seed=0, tiles=(0,), precision=0, tol=None):
+    """precision 1 (bf16 operands): besides the rows at `tol` against the fp64 result of the unrounded operands, an `_exact` row per
+    destination against the fp64 result of the bf16-rounded operands (tests/bf16_exact.py) at the fp32 datapath's bounds."""
     tol = tol or TOL_OP
     out = []
     rng = np.random.default_rng(seed)
@@ -138,6 +159,10 @@ def check_conv(cases=None, seed=0, tiles=(0,), precision=0, tol=None):
         dy = rnd(rng, *y.shape)
         (y * dy).sum().backward()
         geom = K.ConvGeom(k, s, p)
+        if precision == 1:      # bias stays fp32 in the kernels; x / w / dy are multiplied as bf16
+            yq, dxq, dwq = _conv_grads(rne(x), rne(w), b.float().double(), rne(dy), k, s, p, pa)
+            dw32 = None
+            wtol = wgrad_tol(N, *y.shape[1:4])
         for tile in tiles:
             tag = name + ('' if tile == 0 else '_t%x' % tile)
             xd, wd_, bd, dyd = dev(x), dev(w), dev(b), dev(dy)
@@ -149,12 +174,14 @@ def check_conv(cases=None, seed=0, tiles=(0,), precision=0, tol=None):
                     yd2 = torch.empty(y.shape, device=DEV, dtype=torch.float32)
                     K.conv(lib.CONV_FPROP, geom, xd, yd2, wtp, bias=bd, tile=tile, precision=1, w16=wtp.to(torch.bfloat16))
                     out.append((tag + '/fprop_ring', rel_err(yd2, y), tol))
+                    out.append((tag + '/fprop_ring_exact', rel_err(yd2, yq), TOL_EXACT))
                 except RuntimeError:
                     pass
                 try:
                     dx2 = torch.full(x.shape, float('nan'), device=DEV, dtype=torch.float32)
                     K.conv(lib.CONV_DGRAD, geom, dx2, dyd, wdp, tile=tile, precision=1, w16=wdp.to(torch.bfloat16))
                     out.append((tag + '/dgrad_ring', rel_err(dx2, x.grad), tol))
+                    out.append((tag + '/dgrad_ring_exact', rel_err(dx2, dxq), TOL_EXACT))
                 except RuntimeError:
                     pass
                 continue
@@ -173,33 +200,49 @@ def check_conv(cases=None, seed=0, tiles=(0,), precision=0, tol=None):
                 wtp = dev(pack_wt(w.detach()))
                 K.conv(lib.CONV_FPROP, geom, xd, yd2, wtp, bias=bd, tile=tile, precision=1, w16=wtp.to(torch.bfloat16))
                 out.append((tag + '/fprop_w16', rel_err(yd2, y), tol))
+                out.append((tag + '/fprop_w16_exact', rel_err(yd2, yq), TOL_EXACT))
                 dx2 = torch.full(x.shape, float('nan'), device=DEV, dtype=torch.float32)
                 wdp = dev(pack_wd(w.detach()))
                 K.conv(lib.CONV_DGRAD, geom, dx2, dyd, wdp, tile=tile, precision=1, w16=wdp.to(torch.bfloat16))
                 out.append((tag + '/dgrad_w16', rel_err(dx2, x.grad), tol))
+                out.append((tag + '/dgrad_w16_exact', rel_err(dx2, dxq), TOL_EXACT))
                 continue
             # FPROP (+bias)
             yd = torch.empty(y.shape, device=DEV, dtype=torch.float32)
             K.conv(lib.CONV_FPROP, geom, xd, yd, dev(pack_wt(w.detach())), bias=bd, tile=tile, precision=precision)
             out.append((tag + '/fprop', rel_err(yd, y), tol))
+            if precision == 1:      # the fp32 weight stream is converted in the kernel: RNE (conv_igemm.hip, stage())
+                out.append((tag + '/fprop_exact', rel_err(yd, yq), TOL_EXACT))
             if precision == 1:      # bf16 pre-packed weight stream
                 yd2 = torch.empty(y.shape, device=DEV, dtype=torch.float32)
                 wtp = dev(pack_wt(w.detach()))
                 K.conv(lib.CONV_FPROP, geom, xd, yd2, wtp, bias=bd, tile=tile, precision=1, w16=wtp.to(torch.bfloat16))
                 out.append((tag + '/fprop_w16', rel_err(yd2, y), tol))
+                out.append((tag + '/fprop_w16_exact', rel_err(yd2, yq), TOL_EXACT))
                 dx2 = torch.full(x.shape, float('nan'), device=DEV, dtype=torch.float32)
                 wdp = dev(pack_wd(w.detach()))
                 K.conv(lib.CONV_DGRAD, geom, dx2, dyd, wdp, tile=tile, precision=1, w16=wdp.to(torch.bfloat16))
                 out.append((tag + '/dgrad_w16', rel_err(dx2, x.grad), tol))
+                out.append((tag + '/dgrad_w16_exact', rel_err(dx2, dxq), TOL_EXACT))
             # DGRAD
             dxd = torch.full(x.shape, float('nan'), device=DEV, dtype=torch.float32)
             K.conv(lib.CONV_DGRAD, geom, dxd, dyd, dev(pack_wd(w.detach())), tile=tile, precision=precision)
             out.append((tag + '/dgrad', rel_err(dxd, x.grad), tol))
+            if precision == 1:
+                out.append((tag + '/dgrad_exact', rel_err(dxd, dxq), TOL_EXACT))
             # WGRAD
             dwd = torch.zeros(w.shape, device=DEV, dtype=torch.float32)
             dbd = torch.zeros(Cy, device=DEV, dtype=torch.float32)
             K.conv(lib.CONV_WGRAD, geom, xd, dyd, dwd, bias=dbd, tile=tile, precision=precision)
             out.append((tag + '/wgrad', rel_err(dwd, w.grad), tol))
+            if precision == 1:
+                a = K._fill_conv_args(lib.CONV_WGRAD, geom, xd, dyd, dwd, dbd, 0, 0, 0.0, None, 0, tile, 1, None, None)
+                if wgrad_rounds_operands(a):
+                    out.append((tag + '/wgrad_exact', rel_err(dwd, dwq), wtol))
+                else:                   # exact fp32 generic kernel (see wgrad_rounds_operands)
+                    if dw32 is None:
+                        dw32 = _conv_grads(x.float().double(), w, b, dy.float().double(), k, s, p, pa)[2]
+                    out.append((tag + '/wgrad_exact_fp32_operands', rel_err(dwd, dw32), wtol))
             out.append((tag + '/wgrad_bias', rel_err(dbd, b.grad), TOL_OP))
     torch.cuda.synchronize()
     return out
@@ -865,7 +908,8 @@ def check_warp_dna(seed=8):
 
 
 def check_conv_bf16():
-    """bf16-operand / fp32-accumulate mode of the implicit-GEMM kernel: per-op rel <= 1e-2."""
+    """bf16-operand / fp32-accumulate mode of the implicit-GEMM kernel: per-op rel <= 1e-2 against the unrounded
+    operands, and the `_exact` rows of check_conv against the rounded ones."""
     res = check_conv(precision=1, tol=1e-2, tiles=(0, 0x22, 0x11, 0x212, 0x221, 0x122, 0x612, 0x621, 0x611,
                                                    0x311, 0x312, 0x321, 0x322, 0x711, 0x712, 0x721, 0x722))
     # 0x2xx: LDS patch kernel (0x6xx: 8 waves), 0x1xx: generic, 0x3xx / 0x7xx: LDS-DMA ring kernel (4 / 8 waves)
@@ -884,6 +928,8 @@ def check_conv_thin(seed=23):
     wide = torch.full((N,) + dhw + (48,), 7.0, device=DEV)
     K.conv(lib.CONV_FPROP, geom, dev(x), wide[..., 8:40], dev(pack_wt(w)), bias=dev(b), act=lib.ACT_LRELU, alpha=0.2, precision=1)
     out.append(('thin/fprop_lrelu_slice', rel_err(wide[..., 8:40], y), 1e-2))
+    yq = torch.nn.functional.leaky_relu(_ref_conv(rne(x), rne(w), k, (1, 1, 1), (1, 1, 1), (1, 1, 1)) + b.float().double(), 0.2)
+    out.append(('thin/fprop_lrelu_slice_exact', rel_err(wide[..., 8:40], yq), TOL_EXACT))
     untouched = bool((wide[..., :8] == 7.0).all() and (wide[..., 40:] == 7.0).all())
     out.append(('thin/fprop_slice_untouched', 0.0 if untouched else 1.0, 0.5))
     dy = rnd(rng, N, *dhw, Cy)
@@ -892,12 +938,16 @@ def check_conv_thin(seed=23):
     K.conv(lib.CONV_WGRAD, geom, dev(x), dev(dy), dwd, bias=dbd, precision=1)
     xp = torch.nn.functional.pad(x.permute(0, 4, 1, 2, 3), (1, 1, 1, 1, 1, 1))
     ref_dw = torch.zeros(*k, Cx, Cy, dtype=torch.float64)
+    ref_dwq = torch.zeros(*k, Cx, Cy, dtype=torch.float64)
+    xpq, dyq = rne(xp), rne(dy)
     for a in range(3):
         for u in range(3):
             for v in range(3):
                 xs = xp[:, :, a:a + dhw[0], u:u + dhw[1], v:v + dhw[2]]           # [N, Cx, D, H, W]
                 ref_dw[a, u, v] = torch.einsum('ncdhw,ndhwo->co', xs, dy)
+                ref_dwq[a, u, v] = torch.einsum('ncdhw,ndhwo->co', xpq[:, :, a:a + dhw[0], u:u + dhw[1], v:v + dhw[2]], dyq)
     out.append(('thin/wgrad_accumulates', rel_err(dwd, dw0 + ref_dw), 1e-2))
+    out.append(('thin/wgrad_accumulates_exact', rel_err(dwd, dw0.float().double() + ref_dwq), wgrad_tol(N, *dhw)))
     out.append(('thin/wgrad_bias_accumulates', rel_err(dbd, db0 + dy.sum(dim=(0, 1, 2, 3))), TOL_OP))
     # conv_s2dgrad.hip: data gradient of the 4x4 stride-(1,2,2) layer into a 32-channel activation; ragged tiles, accumulation into
     # the destination (beta) and the fused LeakyReLU backward from the saved activation; 3-D (kd = 4) and 2-D (kd = 1, Cy = 32)
@@ -912,13 +962,17 @@ def check_conv_thin(seed=23):
         old = rnd(rng, N, *dhw, 32)
         aux = rnd(rng, N, *dhw, 32)
         ref = x.grad + (old if beta else 0.0)
+        # exact: dy and w as bf16; the old gradient (beta) and the saved activation stay fp32 in the kernel
+        refq = _conv_grads(x, rne(w), torch.zeros(()), rne(dy), k, s_, pp, pp)[1] + (old.float().double() if beta else 0.0)
         if act:
             ref = ref * torch.where(aux > 0, torch.ones_like(aux), torch.full_like(aux, 0.1))
+            refq = refq * torch.where(aux.float() > 0, torch.ones_like(aux), torch.full_like(aux, 0.1))
         dxd = dev(old) if beta else torch.full(x.shape, float('nan'), device=DEV)
         wdp = dev(pack_wd(w))
         K.conv(lib.CONV_DGRAD, K.ConvGeom(k, s_, pp), dxd, dev(dy), wdp, beta=beta, act=lib.ACT_DLRELU_FROM_OUT if act else 0, alpha=0.1,
                aux=dev(aux) if act else None, precision=1, w16=wdp.to(torch.bfloat16))
         out.append((tag, rel_err(dxd, ref), 1e-2))
+        out.append((tag + '_exact', rel_err(dxd, refq), TOL_EXACT))
     torch.cuda.synchronize()
     return out
 
@@ -937,6 +991,8 @@ def check_conv_cell(seed=21):
         g2, b2 = rnd(rng, F) * 0.3 + 1, rnd(rng, F) * 0.3
         gates = TF.conv2d(x, w, (1, 1), 'SAME')
         cn, hn = _ref_lstm_gates(gates, c, g1, b1, g2, b2)
+        gates_q = TF.conv2d(rne(x), rne(w), (1, 1), 'SAME')           # the kernel's operands: x and w as bf16
+        ref_sq = torch.stack([gates_q.sum(dim=(1, 2)), (gates_q ** 2).sum(dim=(1, 2))], dim=-1)    # of the fp32 accumulators
         tag = 'cell_%dx%dx%d' % (H, W, F)
         geom = K.ConvGeom((5, 5), (1, 1), (2, 2))
         wt = dev(pack_wt(w))
@@ -948,6 +1004,7 @@ def check_conv_cell(seed=21):
             ws.zero_()
             K.conv(lib.CONV_FPROP, geom, xd, yd, wt, precision=1, w16=wt.to(torch.bfloat16), stats=s1)
             out.append((t2 + '/gates_bf16', rel_err(yd.float(), gates), 1e-2))
+            out += bracket_rows(t2 + '/gates_bf16_exact', yd, gates_q)
             if Cx > 96:        # wide weight slabs (tile bit 0x1000: 8 / 9 k-steps per entry): same sums in another slab order
                 for wide in (0x1311, 0x1711):
                     yw = torch.empty_like(yd)
@@ -958,9 +1015,14 @@ def check_conv_cell(seed=21):
                         continue                       # this workgroup size cannot hold the wider ring (LDS)
                     out.append((t2 + '/wide%x_gates_bf16' % wide, rel_err(yw.float(), gates), 1e-2))
                     out.append((t2 + '/wide%x_stats_sum' % wide, rel_err(sw[..., 0], torch.stack([gates.sum(dim=(1, 2))], dim=-1)[..., 0]), 1e-2))
+                    out += bracket_rows(t2 + '/wide%x_gates_bf16_exact' % wide, yw, gates_q)
+                    out.append((t2 + '/wide%x_stats_sum_exact' % wide, rel_err(sw[..., 0], ref_sq[..., 0]), TOL_EXACT))
+                    out.append((t2 + '/wide%x_stats_sumsq_exact' % wide, rel_err(sw[..., 1], ref_sq[..., 1]), TOL_EXACT))
             ref_s = torch.stack([gates.sum(dim=(1, 2)), (gates ** 2).sum(dim=(1, 2))], dim=-1)         # [N, 4F, 2]
             out.append((t2 + '/stats_sum', rel_err(s1[..., 0], ref_s[..., 0]), 1e-2))
             out.append((t2 + '/stats_sumsq', rel_err(s1[..., 1], ref_s[..., 1]), 1e-2))
+            out.append((t2 + '/stats_sum_exact', rel_err(s1[..., 0], ref_sq[..., 0]), TOL_EXACT))
+            out.append((t2 + '/stats_sumsq_exact', rel_err(s1[..., 1], ref_sq[..., 1]), TOL_EXACT))
             p = [dev(t) for t in (g1, b1, g2, b2)]
             c_new = torch.empty(N, H, W, F, device=DEV)
             h1 = torch.empty(N, H, W, F, device=DEV)
@@ -1041,6 +1103,7 @@ def check_gate_conv_kernel(seed=67):
             res.append((yd.clone(), s1.clone()))
         yd, s1 = res[0]
         out.append((tag + '/gates_vs_fp64', rel_err(yd.float(), ref), 6e-3))          # bf16 rounding of the result: 2^-9 relative to the element
+        out += bracket_rows(tag + '/gates_vs_fp64', yd, ref)                            # ... and elementwise: RNE of the exact sum
         out.append((tag + '/stats_sum', rel_err(s1[..., 0], ref_s[..., 0]), 2e-5))      # the sums are taken of the fp32 accumulators
         out.append((tag + '/stats_sumsq', rel_err(s1[..., 1], ref_s[..., 1]), 2e-5))
         out.append((tag + '/repeat_bits', float((res[1][0].view(torch.int16) != yd.view(torch.int16)).sum() + (res[1][1] != s1).sum()), 0.0))
@@ -1053,6 +1116,8 @@ def check_gate_conv_kernel(seed=67):
         finally:
             lib.set_option('gate_kernel', 1)
         out.append((tag + '/vs_ring_gates', rel_err(yd.float(), yr.float()), 8e-3))     # both round the same fp32 sums (other order) to bf16
+        # ... so element by element at most one bf16 ulp apart beyond the two fp32 sums' own distance (tests/bf16_exact.py window)
+        out.append((tag + '/vs_ring_gates_apart', bf16_apart(yd.cpu(), yr.cpu(), 2 * window(ref)), 0.0))
         out.append((tag + '/vs_ring_stats', rel_err(s1, sr), 2e-5))
     torch.cuda.synchronize()
     return out
@@ -1109,13 +1174,14 @@ def check_one_launch_cell(seed=71):
                 ga = K.convlstm_gates_fwd(yd, None if zero_state else dev(c), p[0], p[1], p[2], p[3], c_new, hs, stats, ws=lws, stats1=ws, defer=True)
                 K.convlstm_cell_fwd(ca, ga)
                 torch.cuda.synchronize()
-                res[mode] = dict(y=yd.float().cpu(), c=c_new.cpu(), h=[h.float().cpu() for h in hs], st=[t.cpu() for t in stats],
+                res[mode] = dict(y=yd.float().cpu(), y16=yd.cpu(), c=c_new.cpu(), h=[h.float().cpu() for h in hs], st=[t.cpu() for t in stats],
                                  one_launch=bool(float(s1.abs().sum()) == 0.0))
             finally:
                 lib.set_option('gate_cell', 1)
         out.append((tag + '/is_one_launch', 0.0 if (res[1]['one_launch'] and not res[0]['one_launch']) else 1.0, 0.0))
         r = res[1]
         out.append((tag + '/gates_bf16', rel_err(r['y'], gates), 6e-3))
+        out += bracket_rows(tag + '/gates_bf16_exact', r['y16'], gates)                # gates: fp64 of the bf16 operands already
         out.append((tag + '/c', rel_err(r['c'], cn), 2e-2))
         for k, h in enumerate(r['h']):
             out.append((tag + '/h%d' % k, rel_err(h, hn), 2e-2))
@@ -1361,6 +1427,9 @@ def check_conv_stats_fp32(seed=43):
         bias = rn(cdst) + (300.0 if 'bigbias' in name else 0.0)
         ref = _taps_ref(mode, x32, w32, y32, k, s, p) + bias                     # [N, 1, h, w, cdst]
         ref = ref[:, 0]
+        refq = _taps_ref(mode, rne(x32).double(), rne(w32).double(), rne(y32).double(), k, s, p)[:, 0]     # exact, around the bias
+        r2q = refq.reshape(N, -1, cdst)
+        refq = refq + bias.double()
         geom = K.ConvGeom(k, s, p)
         wp = (pack_wt(w32) if fprop else pack_wd(w32)).contiguous()
         gam, bet = rn(cdst) * 0.3 + 1, rn(cdst) * 0.3
@@ -1381,6 +1450,9 @@ def check_conv_stats_fp32(seed=43):
             r2 = (ref - bias).reshape(N, -1, cdst)                   # the sums are taken around the bias
             out.append((tag + '/sum', rel_err(stats[..., 0], r2.sum(1)), 1e-2))
             out.append((tag + '/sumsq', rel_err(stats[..., 1], (r2 * r2).sum(1)), 1e-2))
+            out.append((tag + '/out_exact', rel_err(dst, refq), TOL_EXACT))
+            out.append((tag + '/sum_exact', rel_err(stats[..., 0], r2q.sum(1)), TOL_EXACT))
+            out.append((tag + '/sumsq_exact', rel_err(stats[..., 1], (r2q * r2q).sum(1)), TOL_EXACT))
             o1 = torch.empty_like(dst)
             mean, rstd = torch.empty(N, cdst, device=DEV), torch.empty(N, cdst, device=DEV)
             K.instnorm_act_fwd(dst, gam, bet, [o1], mean, rstd, act='relu', stats=stats, stats_shift=bias)
@@ -1567,6 +1639,7 @@ def check_wide_thin_fprop(seed=59):
                     out.append(('wthin_%s/neighbours_untouched' % name, float((big[..., mask] - 7.0).abs().max()), 0.5))
             out.append(('wthin_%s/vs_fp64_taps' % name, rel_err(res[0], ref), 2e-5))
             out.append(('wthin_%s/vs_general_kernels' % name, rel_err(res[0], res[1].double().cpu()), 2e-5))
+            out.append(('wthin_%s/general_kernels_vs_fp64_taps' % name, rel_err(res[1], ref), TOL_EXACT))
     finally:
         lib.set_option('thin', old)
     torch.cuda.synchronize()
@@ -1609,6 +1682,7 @@ def check_thin8_wide_dgrad(seed=61):
                     out.append(('thin8_%s/neighbours_untouched' % name, float((big[..., :xw - Cx] - 7.0).abs().max()), 0.5))
             out.append(('thin8_%s/vs_fp64_taps' % name, rel_err(res[0], ref), 2e-5))
             out.append(('thin8_%s/vs_general_kernels' % name, rel_err(res[0], res[1].double().cpu()), 2e-5))
+            out.append(('thin8_%s/general_kernels_vs_fp64_taps' % name, rel_err(res[1], ref), TOL_EXACT))
     finally:
         lib.set_option('thin', old)
     torch.cuda.synchronize()
@@ -1617,7 +1691,10 @@ def check_thin8_wide_dgrad(seed=61):
 
 def check_tuning_table(precision='bf16', max_entries=None, seed=41):
     """Runs every entry of video_prediction_amd/tuning_gfx950_<precision>.json as that exact savp_conv call (mode, shapes, view
-    strides, bias / w16 / act / beta / bf16 source / bf16 destination / statistics epilogue, the table's tile code and split-K)."""
+    strides, bias / w16 / act / beta / bf16 source / bf16 destination / statistics epilogue, the table's tile code and split-K).
+    bf16 table: every entry (and its statistics) also gets `_exact` rows against the fp64 tap loop of the bf16-rounded operands the kernel
+    multiplies (x, w, dy as the call has them; bias, the old destination under beta and aux stay fp32) at the fp32 datapath's bounds,
+    or, for a bf16 destination, the bracket / RNE rows of tests/bf16_exact.py."""
     import ast
     import json
     import os
@@ -1626,6 +1703,16 @@ def check_tuning_table(precision='bf16', max_entries=None, seed=41):
     prec = 1 if precision == 'bf16' else 0
     out = []
     rng = torch.Generator(device=DEV).manual_seed(seed)
+    # the exact rows' reference runs in fp32 (rocBLAS sgemm): bf16 x bf16 products are exact there, only the sums round (~1e-7,
+    # cross-checked against fp64 on the first entry of each mode); a tf32 matmul would round the operands and void that
+    assert not torch.backends.cuda.matmul.allow_tf32
+    checked64 = set()
+
+    def cross_check(refq, mode, xq, wq, yq):
+        if mode not in checked64:
+            checked64.add(mode)
+            r64 = _taps_ref(mode, xq.double(), wq.double(), yq.double(), k, s, p)
+            out.append(('table_%s/m%d_exact_fp32_reference_vs_fp64' % (precision, mode), rel_err(refq, r64), 0.1 * TOL_EXACT))
 
     def rn(*shape):
         return torch.randn(*shape, generator=rng, device=DEV, dtype=torch.float32)
@@ -1689,6 +1776,13 @@ def check_tuning_table(precision='bf16', max_entries=None, seed=41):
                 db = torch.zeros(Cy, device=DEV) if has_b else None
                 K.conv(mode, geom, xv, yv, dw, bias=db, splitk=sk, tile=tile, precision=prec)
                 out.append((tag + '/wgrad', rel_err(dw, ref), 1e-2 if prec else 2e-5 * max(1.0, (N * Do * Ho * Wo / 65536.0) ** 0.5)))
+                if prec:
+                    a = K._fill_conv_args(mode, geom, xv, yv, dw, db, 0, 0, 0.0, None, sk, tile, prec, None, None)
+                    q = rne if wgrad_rounds_operands(a) else (lambda t: t)          # else: the exact-fp32 generic kernel
+                    refq = _taps_ref(mode, q(x32), w32, q(y32), k, s, p)
+                    cross_check(refq, mode, q(x32), w32, q(y32))
+                    out.append((tag + '/wgrad_exact', rel_err(dw, refq), wgrad_tol(N, Do, Ho, Wo)))
+                    del refq
                 if has_b:
                     out.append((tag + '/wgrad_bias', rel_err(db, y64.reshape(-1, Cy).sum(0)), 1e-4))
                 continue
@@ -1696,6 +1790,10 @@ def check_tuning_table(precision='bf16', max_entries=None, seed=41):
             dst_shape = (N, Do, Ho, Wo, Cy) if fprop else (N, D, H, W, Cx)
             cdst = dst_shape[-1]
             ref = _taps_ref(mode, x64, w64, y64, k, s, p)
+            # exact reference (bf16 table): the source and the weights as bf16, the rest of the epilogue as below, in fp64
+            refq = _taps_ref(mode, rne(x32), rne(w32), rne(y32), k, s, p).double() if prec else None
+            if prec:
+                cross_check(refq, mode, rne(x32), rne(w32), rne(y32))
             bias = rn(cdst) if has_b else None
             dst = yv if fprop else xv
             old = None
@@ -1706,31 +1804,119 @@ def check_tuning_table(precision='bf16', max_entries=None, seed=41):
                 dst.fill_(float('nan'))
             if bias is not None:
                 ref = ref + bias.to(rdt)
+            if prec:
+                refq = refq + (old.double() if beta else 0.0)
+                sumq = refq                                          # the statistics are taken around the bias
+                refq = refq + (bias.double() if bias is not None else 0.0)
             aux = None
             if act == lib.ACT_LRELU:
                 ref = torch.where(ref > 0, ref, alpha * ref)
+                refq = torch.where(refq > 0, refq, alpha * refq) if prec else None
             elif act == lib.ACT_SIGMOID:
                 ref = torch.sigmoid(ref)
+                refq = torch.sigmoid(refq) if prec else None
             elif act == lib.ACT_DLRELU_FROM_OUT:
                 a32 = rn(*dst_shape)
                 aux = strided(dst_shape, (y_sw if fprop else x_sw), torch.float32, a32)
                 ref = ref * torch.where(a32 > 0, torch.ones_like(ref), torch.full_like(ref, alpha))
+                refq = refq * torch.where(a32 > 0, 1.0, alpha).double() if prec else None
             wp = (pack_wt(w32) if fprop else pack_wd(w32)).contiguous()
             stats = torch.zeros(N, cdst, 2, device=DEV, dtype=torch.float64) if has_stats else None
             K.conv(mode, geom, xv, yv, wp, bias=bias, beta=beta, act=act, alpha=alpha, aux=aux, splitk=sk, tile=tile, precision=prec,
                    w16=wp.to(bf) if has_w16 else None, stats=stats, dst_gap=gap)
             got = dst.float().reshape(dst_shape)
             refd = ref.reshape(dst_shape)
+            got16, refqd = dst.reshape(dst_shape), (refq.reshape(dst_shape) if prec else None)
             if gap is not None:                      # the gap's channels are not computed: compare the logical ones
                 keep = [c for c in range(dst_shape[-1]) if not (gap[0] <= c < gap[0] + gap[1])]
                 got, refd = got[..., keep], refd[..., keep]
-            out.append((tag + ('/fprop' if fprop else '/dgrad') + ('_gap' if gap else ''), rel_err(got, refd), 1e-2 if prec else 2e-5))
+                if prec:
+                    got16, refqd = got16[..., keep], refqd[..., keep]
+            row = tag + ('/fprop' if fprop else '/dgrad') + ('_gap' if gap else '')
+            out.append((row, rel_err(got, refd), 1e-2 if prec else 2e-5))
+            if prec and dst.dtype == bf:
+                out += bracket_rows(row + '_exact', got16, refqd)
+            elif prec:
+                out.append((row + '_exact', rel_err(got, refqd), TOL_EXACT))
             if has_stats:
                 r2 = (ref - bias.to(rdt) if bias is not None else ref).reshape(N, -1, cdst)        # sums are taken around the bias
                 out.append((tag + '/stats_sum', rel_err(stats[..., 0], r2.sum(1)), 1e-2))
                 out.append((tag + '/stats_sumsq', rel_err(stats[..., 1], (r2 * r2).sum(1)), 1e-2))
+                if prec:
+                    r2q = sumq.reshape(N, -1, cdst)                  # of the fp32 accumulators, not of the (bf16) destination
+                    out.append((tag + '/stats_sum_exact', rel_err(stats[..., 0], r2q.sum(1)), TOL_EXACT))
+                    out.append((tag + '/stats_sumsq_exact', rel_err(stats[..., 1], (r2q * r2q).sum(1)), TOL_EXACT))
         except RuntimeError as ex:
             out.append((tag + '/REFUSED:%s' % str(ex)[:60], float('inf'), 0.0))
+    torch.cuda.synchronize()
+    return out
+
+
+RING_TILES = (0x311, 0x312, 0x321, 0x322, 0x711, 0x712, 0x721, 0x722)
+
+
+def check_ring_splitk_sweep(seed=73):
+    """Ragged split-K on the bf16 datapath: the CONV_CASES the ring kernel takes (lstm5x5_*, s1_odd*, enc4x4s2, pool*), split-K forced
+    to 2 / 3 / 5 / 16 for FPROP and DGRAD under every ring tile code (conv_ring.hip: one scratch slice per split, folded in split order)
+    and for WGRAD under the generic kernel's tile codes (deterministic per-split slices, conv_igemm.hip) and a ring code (the LDS-patch
+    kernel).  Each call: the exact rows of tests/bf16_exact.py, two runs bit-identical (the fixed-order fold), a destination pre-filled
+    with NaN comes back NaN-free, and for FPROP / DGRAD a third run accumulating into an fp32 destination (beta = 1).  A combination the
+    launcher refuses raises RuntimeError and is skipped; every (case, mode) must have run at least one split call."""
+    out = []
+    rng = np.random.default_rng(seed)
+    names = [c for c in CONV_CASES if c[0].startswith(('lstm5x5_', 's1_odd', 'enc4x4s2', 'pool'))]
+    for name, N, dhw, Cx, Cy, k, s, p, pa in names:
+        x, w = rnd(rng, N, *dhw, Cx), rnd(rng, *k, Cx, Cy) * 0.1
+        odhw = tuple((i + pb + pe - kk) // st + 1 for i, pb, pe, kk, st in zip(dhw, p, pa, k, s))
+        dy0 = rnd(rng, N, *odhw, Cy)
+        yq, dxq, dwq = _conv_grads(rne(x), rne(w), torch.zeros(()), rne(dy0), k, s, p, pa)
+        geom = K.ConvGeom(k, s, p)
+        xd, dyd = dev(x), dev(dy0)
+        wt, wd = dev(pack_wt(w)), dev(pack_wd(w))
+        old_x, old_y = dev(rnd(rng, *x.shape)), dev(rnd(rng, *dy0.shape))
+        wtol = wgrad_tol(N, *odhw)
+        for mode, mname, tiles in ((lib.CONV_FPROP, 'fprop', RING_TILES), (lib.CONV_DGRAD, 'dgrad', RING_TILES),
+                                   (lib.CONV_WGRAD, 'wgrad', (0x111, 0x122, 0x311))):
+            ran = 0
+            for tile in tiles:
+                for sk in (2, 3, 5, 16):
+                    tag = 'splitk/%s_%s_t%x_sk%d' % (name, mname, tile, sk)
+                    res = []
+                    try:
+                        for rep in range(2):
+                            if mode == lib.CONV_FPROP:
+                                dst = torch.full(yq.shape, float('nan'), device=DEV)
+                                K.conv(mode, geom, xd, dst, wt, tile=tile, splitk=sk, precision=1, w16=wt.to(torch.bfloat16))
+                            elif mode == lib.CONV_DGRAD:
+                                dst = torch.full(x.shape, float('nan'), device=DEV)
+                                K.conv(mode, geom, dst, dyd, wd, tile=tile, splitk=sk, precision=1, w16=wd.to(torch.bfloat16))
+                            else:
+                                dst = torch.zeros(w.shape, device=DEV)
+                                K.conv(mode, geom, xd, dyd, dst, tile=tile, splitk=sk, precision=1)
+                            res.append(dst)
+                    except RuntimeError:
+                        continue                                     # the launcher refuses this combination
+                    ran += 1
+                    got = res[0]
+                    if mode == lib.CONV_WGRAD:
+                        a = K._fill_conv_args(mode, geom, xd, dyd, got, None, 0, 0, 0.0, None, sk, tile, 1, None, None)
+                        ref = dwq if wgrad_rounds_operands(a) else _conv_grads(x.float().double(), w, torch.zeros(()),
+                                                                               dy0.float().double(), k, s, p, pa)[2]
+                        out.append((tag + '/exact', rel_err(got, ref), wtol))
+                    else:
+                        out.append((tag + '/exact', rel_err(got, yq if mode == lib.CONV_FPROP else dxq), TOL_EXACT))
+                        out.append((tag + '/nan_free', 0.0 if bool(torch.isfinite(got).all()) else 1.0, 0.5))
+                        old = old_y if mode == lib.CONV_FPROP else old_x
+                        acc = old.clone()
+                        if mode == lib.CONV_FPROP:
+                            K.conv(mode, geom, xd, acc, wt, beta=1, tile=tile, splitk=sk, precision=1, w16=wt.to(torch.bfloat16))
+                            ref = yq + old.double().cpu()
+                        else:
+                            K.conv(mode, geom, acc, dyd, wd, beta=1, tile=tile, splitk=sk, precision=1, w16=wd.to(torch.bfloat16))
+                            ref = dxq + old.double().cpu()
+                        out.append((tag + '/beta_exact', rel_err(acc, ref), TOL_EXACT))
+                    out.append((tag + '/repeat_bits', 0.0 if torch.equal(res[0], res[1]) else 1.0, 0.5))
+            out.append(('splitk/%s_%s/ran' % (name, mname), 0.0 if ran else 1.0, 0.5))
     torch.cuda.synchronize()
     return out
 

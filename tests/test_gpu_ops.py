@@ -160,12 +160,18 @@ def test_metric_kernels_against_committed_golden():
 @pytest.mark.parametrize('precision', ['bf16', 'f32'])
 def test_every_shipped_tuning_table_instantiation_vs_fp64(precision):
     """The (problem, tile, split-K) pairs bench.py actually launches (video_prediction_amd/tuning_gfx950_*.json, N = 32 / 464 / 928 ...
-    at their own shapes), each against an fp64 tap-loop reference: rel <= 1e-2 (bf16 operands) / 2e-5 (exact fp32)."""
+    at their own shapes), each against an fp64 tap-loop reference: rel <= 1e-2 (bf16 operands) / 2e-5 (exact fp32); bf16 entries also
+    against the reference of their bf16-rounded operands at the fp32 bounds (tests/bf16_exact.py)."""
     from tests import gpu_checks
     res = gpu_checks.check_tuning_table(precision)
     assert len(res) >= 90
     bad = gpu_checks.failures(res)
     assert not bad, 'parity failures (name, rel err, tol): %r' % bad[:20]
+
+
+def test_ring_kernel_ragged_split_k_bf16_exact_and_reproducible():
+    from tests import gpu_checks
+    _run(gpu_checks.check_ring_splitk_sweep)
 
 
 def test_tiled_z_gradient_and_gapped_gate_dgrad():
