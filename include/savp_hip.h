@@ -541,6 +541,28 @@ int savp_eval_accumulate(void* stream, const float* metric, float* vmin, float* 
 int savp_select_batch(void* stream, const int32_t* cond, const float* x, int64_t x_st, int64_t x_sb, float* out, int64_t o_st,
                       int64_t o_sb, int32_t T, int32_t B, int32_t inner, int32_t mode);
 
+/* The best-of-N fold over S prior samples at once (eval_outputs_and_metrics with parallel_iterations = S > 1).  target = the future frames
+ * [F, B, H, W, C]; pred = one chunk's prior unroll [T1, S*B, H, W, C], sample-major rows n = s*B + b, whose last F frames are the future.
+ * For every (f, s, b) it computes psnr / mse / ssim exactly as savp_frame_mse_psnr / savp_frame_ssim do on the same frames (same device code;
+ * the ssim channel shares are summed c = 0, 1, ... in order instead of by atomics), then folds s = 0 .. *n_valid - 1 in ascending order into
+ * states[k] (k = SAVP_EVAL_PSNR / _MSE / _SSIM) with the rule of savp_eval_accumulate + savp_select_batch: strict < / > on the time-mean
+ * (ties keep the earlier sample), vsum / gsum accumulated in fp32 in sample order, the winners' whole T1-frame sequences gathered into
+ * gmin / gmax.  n_valid is an int32 in DEVICE memory (0 .. S; samples past it are padding and never read), so one captured launch sequence
+ * serves a padded last chunk too.  ws: savp_eval_fold_ws_floats(F, S, B, C) floats of scratch; on return its first 3*F*S*B floats hold the
+ * per-frame metrics [k][f][s*B + b] of the valid samples.  No atomics; four launches. */
+#define SAVP_EVAL_PSNR 0
+#define SAVP_EVAL_MSE 1
+#define SAVP_EVAL_SSIM 2
+#define SAVP_EVAL_NMETRICS 3
+typedef struct {
+    float *vmin, *vsum, *vmax;     /* [F, B] contiguous: running min / sum / max of the metric */
+    float *gmin, *gsum, *gmax;     /* [T1, B, H, W, C] contiguous: the sequences chosen by min / max, and the running sum */
+} SavpEvalFoldState;
+int64_t savp_eval_fold_ws_floats(int32_t F, int32_t S, int32_t B, int32_t C);
+int savp_eval_fold_samples(void* stream, const float* target, int64_t t_st, int64_t t_sb, const float* pred, int64_t p_st, int64_t p_sb,
+                           int32_t F, int32_t T1, int32_t S, int32_t B, int32_t H, int32_t W, int32_t C, const int32_t* n_valid,
+                           const SavpEvalFoldState* states, float* ws, int64_t ws_floats);
+
 /* Fold float64 accumulators into fp32 gradients (round 6): dst[i] += (float) src[i] ; src[i] = 0 for i in idx[0 .. n) (idx NULL: i = 0 .. n-1).
  * The parameter gradients that many workgroups add to are accumulated in a float64 twin of the gradient arena (SavpInormArgs.dgamma, ...)
  * and rounded to fp32 once, here, before the optimiser (base_model.py:486-510) or the gradient exchange reads them. */

@@ -74,6 +74,17 @@ def resolve_options(args):
     for kind in ('gif', 'png'):
         if not getattr(args, 'results_%s_dir' % kind):
             setattr(args, 'results_%s_dir' % kind, args.results_dir)
+    dataset_hparams, model_hparams, leaf = read_checkpoint_options(args)
+    for kind in ('gif', 'png'):
+        if not getattr(args, 'output_%s_dir' % kind):
+            setattr(args, 'output_%s_dir' % kind, os.path.join(getattr(args, 'results_%s_dir' % kind), leaf))
+    return dataset_hparams, model_hparams
+
+
+def read_checkpoint_options(args):
+    """args.dataset / args.model (unless given) and the dataset / model hparams dicts from the checkpoint's directory; returns them with
+    the name of the results subdirectory: the checkpoint directory's name, or model.<model> without a checkpoint (shared with
+    scripts/evaluate.py, reference evaluate.py:181-208)."""
     hparams = {'dataset': {}, 'model': {}}
     if args.checkpoint:
         ckpt_dir = os.path.normpath(args.checkpoint)
@@ -94,10 +105,7 @@ def resolve_options(args):
             if not getattr(args, key):
                 raise ValueError('%s is required when checkpoint is not specified' % key)
         leaf = 'model.%s' % args.model
-    for kind in ('gif', 'png'):
-        if not getattr(args, 'output_%s_dir' % kind):
-            setattr(args, 'output_%s_dir' % kind, os.path.join(getattr(args, 'results_%s_dir' % kind), leaf))
-    return hparams['dataset'], hparams['model']
+    return hparams['dataset'], hparams['model'], leaf
 
 
 def write_png(path, image):

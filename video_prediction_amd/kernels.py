@@ -1412,6 +1412,45 @@ def select_batch(cond, x, out, mode=0):
                                      int(mode)), 'savp_select_batch')
 
 
+EVAL_FOLD_KEYS = ('psnr', 'mse', 'ssim')          # savp_eval_fold_samples' metric order (lib.EVAL_PSNR / _MSE / _SSIM)
+
+
+def eval_fold_ws(F, S, B, C, device):
+    """Scratch of eval_fold_samples; its first 3*F*S*B floats are the per-frame metrics [metric][f][s*B + b] after a call."""
+    n = int(_L().savp_eval_fold_ws_floats(int(F), int(S), int(B), int(C)))
+    if n <= 0:
+        raise ValueError('eval_fold_ws: bad shape %r' % ((F, S, B, C),))
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def eval_fold_samples(target, pred, n_valid, states, ws):
+    """base_model.py:176-201 over S prior samples at once: target [F, B, H, W, C] (the future frames), pred [T1, S*B, H, W, C] (sample-
+    major rows), n_valid int32 device tensor [1] (samples of this chunk that count, 0 .. S), states {'psnr' | 'mse' | 'ssim': dict(min, sum,
+    max: [F, B], gmin, gsum, gmax: [T1, B, H, W, C])} updated in place exactly as savp_eval_accumulate + savp_select_batch once per sample
+    would (include/savp_hip.h)."""
+    lib.require_device(target, pred, ws)
+    _require_i32(n_valid)
+    F, B, H, W, C = target.shape
+    T1, SB = pred.shape[:2]
+    if tuple(pred.shape[2:]) != (H, W, C) or SB % B or T1 < F:
+        raise ValueError('eval_fold_samples: pred %r does not fit target %r' % (tuple(pred.shape), tuple(target.shape)))
+    S = SB // B
+    t_st, t_sb, _ = _tb(target)
+    p_st, p_sb, _ = _tb(pred)
+    arr = (lib.SavpEvalFoldState * lib.EVAL_NMETRICS)()
+    for k, name in enumerate(EVAL_FOLD_KEYS):
+        a = states[name]
+        for key, shape in (('min', (F, B)), ('sum', (F, B)), ('max', (F, B)), ('gmin', (T1, B, H, W, C)), ('gsum', (T1, B, H, W, C)),
+                           ('gmax', (T1, B, H, W, C))):
+            v = a[key]
+            lib.require_device(v)
+            if tuple(v.shape) != shape or not v.is_contiguous() or v.dtype != torch.float32:
+                raise ValueError('eval_fold_samples: state %s/%s must be contiguous fp32 %r' % (name, key, shape))
+        arr[k] = lib.SavpEvalFoldState(_p(a['min']), _p(a['sum']), _p(a['max']), _p(a['gmin']), _p(a['gsum']), _p(a['gmax']))
+    lib.check(_L().savp_eval_fold_samples(lib.stream(), _p(target), t_st, t_sb, _p(pred), p_st, p_sb, F, T1, S, B, H, W, C, _p(n_valid),
+                                          arr, _p(ws), ws.numel()), 'savp_eval_fold_samples')
+
+
 def u8_frames_to_f32(frames_u8, out_tm):
     """uint8 [B, T, H, W, C] -> float32 time-major [T, B, H, W, C] / 255 (base_dataset.py:187 + transpose_batch_time)."""
     if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()):

@@ -144,6 +144,7 @@ def _declare(lib):
     _sig(lib, 'savp_tiled_z_weff', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp])
     _sig(lib, 'savp_tiled_z_grad', [c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i64])
     _sig(lib, 'savp_tiled_z_workspace_bytes', [c_i64, c_i32], restype=c_i64)
+    _sig(lib, 'savp_eval_fold_ws_floats', [c_i32, c_i32, c_i32, c_i32], restype=c_i64)
     for name, argtypes in _EXTRA_SIGS.items():
         _sig(lib, name, argtypes)
 
@@ -302,6 +303,17 @@ register('savp_frame_mse_psnr', [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c
 register('savp_frame_ssim', [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp])
 register('savp_eval_accumulate', [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32])
 register('savp_select_batch', [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32])
+
+
+EVAL_PSNR, EVAL_MSE, EVAL_SSIM, EVAL_NMETRICS = 0, 1, 2, 3     # state / per-frame metric order of savp_eval_fold_samples
+
+
+class SavpEvalFoldState(ctypes.Structure):
+    _fields_ = [('vmin', c_vp), ('vsum', c_vp), ('vmax', c_vp), ('gmin', c_vp), ('gsum', c_vp), ('gmax', c_vp)]
+
+
+register('savp_eval_fold_samples', [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                    ctypes.POINTER(SavpEvalFoldState), c_vp, c_i64])
 register('savp_adam', [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp])
 register('savp_cdna_kernels_fwd', [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])
 register('savp_cdna_kernels_bwd', [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])

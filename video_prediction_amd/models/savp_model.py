@@ -763,11 +763,29 @@ class SAVPEngine(object):
         self._frame_metrics(gen[:, self.B:] if self.nz else gen, buf)
         return OrderedDict((k, buf[k].mean()) for k in self.METRICS)
 
-    def eval_outputs_and_metrics(self, num_samples=100, noises=None):
+    def _eval_noise(self, s_i, noises):
+        """The draws of evaluation sample s_i: noises[s_i], or the sample's own seeded stream (the same for every parallel_iterations)."""
+        if noises:
+            return noises[s_i]
+        return self.default_noise(torch.Generator().manual_seed(self._noise_seed(self.step, stream=1 + s_i)))
+
+    def eval_outputs_and_metrics(self, num_samples=100, noises=None, parallel_iterations=1):
         """eval_outputs_and_metrics_fn (base_model.py:132-227): draw num_samples prior unrolls; per metric keep, for every
         sequence, the sample whose time-mean is smallest / largest, and the running mean.  noises: optional list of noise dicts
         (one per sample; default = fresh draws).  Returns (eval_outputs, eval_metrics) with the reference's keys, time-major;
-        the lpips / eval_diversity entries need external network weights and are not produced."""
+        the lpips / eval_diversity entries need external network weights and are not produced.
+        parallel_iterations = S > 1 (the reference's tf.foldl(parallel_iterations=S), base_model.py:199-201): S prior samples per
+        unroll of a generator of batch S*B, folded by one fused kernel (_ParallelPriorEval); sample i sees the same draws as here."""
+        S = int(parallel_iterations or 1)
+        if S < 1:
+            raise ValueError('parallel_iterations must be >= 1, got %r' % (parallel_iterations,))
+        if S > 1 and self.nz:
+            key = (S, K.PRECISION['value'])
+            ev = getattr(self, '_par_eval', {}).get(key)
+            if ev is None:
+                self._par_eval = {key: _ParallelPriorEval(self, S)}      # one sampler at a time: it holds an S*B generator
+                ev = self._par_eval[key]
+            return ev.run(num_samples, noises)
         hp, B, dev = self.hp, self.B, self.device
         fut = self.T - hp.context_frames
         outs, mets = OrderedDict(), OrderedDict()
@@ -803,6 +821,159 @@ class SAVPEngine(object):
         inv = 1.0 / float(num_samples)
         for k in self.METRICS:                                         # (:215-221)
             a = st[k]
+            K.axpby(inv, a['gsum'].reshape(-1), 0.0, a['gsum'].reshape(-1), a['gsum'].reshape(-1))
+            K.axpby(inv, a['sum'].reshape(-1), 0.0, a['sum'].reshape(-1), a['sum'].reshape(-1))
+            outs['eval_gen_images_%s/min' % k] = a['gmin']
+            outs['eval_gen_images_%s/avg' % k] = a['gsum']
+            outs['eval_gen_images_%s/max' % k] = a['gmax']
+            mets['eval_%s/min' % k] = a['min']
+            mets['eval_%s/avg' % k] = a['sum']
+            mets['eval_%s/max' % k] = a['max']
+        return outs, mets
+
+
+class _ParallelPriorEval(object):
+    """eval_outputs_and_metrics with parallel_iterations = S > 1 on a model with a latent (nz > 0).
+
+    A second SAVPGenerator of batch S*B (prior only, inference buffers, the engine's weight store) unrolls S samples at once; rows are
+    sample-major, n = s*B + b.  Per batch: the weights are prepared, the posterior encoder (or the learned prior network) runs once, the
+    images are staged into the S*B layout (source stride 0 over s) and every sample's draws are copied to the device in one transfer.  Per
+    chunk of S samples: one device-to-device copy stages the chunk's draws and its count of valid samples, then ONE launch sequence --
+    z = mu + sigma * eps per sample (the same reparam_fwd launch the sequential path runs, so the same bits), the prior unroll and the fused
+    metric + fold kernel (kernels.eval_fold_samples) -- runs eagerly the first time and as one captured hipGraph afterwards.  A last chunk
+    with fewer than S samples is padded with zero draws that the fold never reads, so every chunk of a batch shape replays the same graph."""
+
+    def __init__(self, eng, S):
+        hp, B, dev = eng.hp, eng.B, eng.device
+        H, W, C = eng.image_shape
+        self.eng, self.S, self.B = eng, S, B
+        self.N = N = S * B
+        T, T1, nz = eng.T, eng.T1, eng.nz
+        self.F = F = T - hp.context_frames
+        self.c1 = hp.context_frames - 1
+        self.gen = SAVPGenerator(eng.store, hp, eng.image_shape, N, train=False, cond=eng.cond)
+        self.images = torch.empty(T, N, H, W, C, device=dev)
+        self.zs = torch.zeros(T1, N, nz, device=dev)
+        gt = torch.zeros(T1, N, dtype=torch.int32)
+        gt[:hp.context_frames] = 1                    # self.ground_truth outside training (savp_model.py:333-334)
+        self.gt = gt.to(dev)
+        self.actions = torch.zeros(T1, N, eng.na, device=dev) if eng.na else None
+        self.states = torch.zeros(T, N, eng.ns, device=dev) if eng.ns else None
+        self.ones = torch.ones(N, dtype=torch.int32, device=dev)
+        # one chunk's draws, flat: eps [S, T1, B, nz] (posterior), then prior [T - context, S*B, nz] or the learned prior's eps [S, T1, B, nz]
+        self.n_eps = 0 if eng.learn_prior else S * T1 * B * nz
+        self.n_second = S * T1 * B * nz if eng.learn_prior else F * N * nz
+        self.stage = torch.zeros(self.n_eps + self.n_second, device=dev)
+        self.n_valid = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.zero_eps = torch.zeros(T1, B, nz, device=dev)
+        self.z_tmp = torch.empty(T1, B, nz, device=dev)
+        self.ls_tmp = torch.empty(T1, B, nz, device=dev)
+        self.ws = K.eval_fold_ws(F, S, B, C, dev)
+        shape = (T1, B, H, W, C)
+        self.st = {k: dict(min=torch.empty(F, B, device=dev), sum=torch.empty(F, B, device=dev), max=torch.empty(F, B, device=dev),
+                           gmin=torch.empty(shape, device=dev), gsum=torch.empty(shape, device=dev), gmax=torch.empty(shape, device=dev))
+                   for k in K.EVAL_FOLD_KEYS}
+        self.graph, self.eager = None, 0
+        self.use_graph = eng.infer_graph
+
+    def _stage_batch(self):
+        """Weights, the latent networks' means / variances and the S*B copies of the images / conditioning inputs of the staged batch."""
+        eng, S, B = self.eng, self.S, self.B
+        self.gen.prep_weights()
+        if eng.learn_prior:
+            eng.prior.prep_weights()
+            eng.prior.forward(eng.images_tm, self.zero_eps, kl=False, actions=eng.actions_tm)
+        else:
+            eng.enc.prep_weights()
+            eng.enc.forward(eng.images_tm, self.zero_eps, kl=False, actions=eng.actions_tm)
+        H, W, C = eng.image_shape
+        for t in range(eng.T):
+            K.select(self.ones, eng.images_tm[t].reshape(1, B * H, W, C).expand(S, B * H, W, C), None,
+                     [self.images[t].reshape(S, B * H, W, C)])
+        for buf, src in ((self.actions, eng.actions_tm), (self.states, eng.states_tm)):
+            if buf is not None:
+                L, _, w = src.shape
+                buf.view(L, S, B, w).copy_(src.unsqueeze(1).expand(L, S, B, w))
+        for a in self.st.values():                     # initializer (base_model.py:201-210)
+            a['min'].fill_(float('inf'))
+            a['max'].fill_(float('-inf'))
+            for k in ('sum', 'gmin', 'gsum', 'gmax'):
+                a[k].zero_()
+
+    def _host_draws(self, num_samples, noises):
+        """All draws of the batch, chunk by chunk: float32 [chunks, stage size] and int32 [chunks] valid-sample counts."""
+        eng, S, B, nz = self.eng, self.S, self.B, self.eng.nz
+        chunks = -(-num_samples // S)
+        flat = torch.zeros(chunks, self.n_eps + self.n_second)
+        nv = torch.zeros(chunks, dtype=torch.int32)
+        for c in range(chunks):
+            nv[c] = min(S, num_samples - c * S)
+            eps = flat[c, :self.n_eps].view(S, eng.T1, B, nz) if self.n_eps else None
+            second = flat[c, self.n_eps:]
+            for s in range(int(nv[c])):
+                noise = eng._eval_noise(c * S + s, noises)
+                if eng.learn_prior:
+                    second.view(S, eng.T1, B, nz)[s] = torch.as_tensor(noise['prior_eps'], dtype=torch.float32)
+                else:
+                    eps[s] = torch.as_tensor(noise['eps'], dtype=torch.float32)
+                    second.view(self.F, S, B, nz)[:, s] = torch.as_tensor(noise['prior'], dtype=torch.float32)
+        return flat, nv
+
+    def _chunk(self):
+        """The launch sequence of one chunk (no host input: the draws and n_valid are in self.stage / self.n_valid)."""
+        eng, S, B, c1 = self.eng, self.S, self.B, self.c1
+        T1, nz = eng.T1, eng.nz
+        if eng.learn_prior:                            # zs = mu_p + sigma_p * prior_eps for all steps (:717-721)
+            peps = self.stage[self.n_eps:].view(S, T1, B, nz)
+            for s in range(S):
+                K.reparam_fwd(eng.prior.mu, eng.prior.ls_raw, peps[s], self.ls_tmp, self.z_tmp)
+                copy_view(self.z_tmp, [self.zs[:, s * B:(s + 1) * B]])
+        else:                                          # [posterior z for the first context_frames-1 steps ; N(0,1)]  (:724-725)
+            eps = self.stage[:self.n_eps].view(S, T1, B, nz)
+            if c1 > 0:
+                for s in range(S):
+                    K.reparam_fwd(eng.enc.mu, eng.enc.ls_raw, eps[s], self.ls_tmp, self.z_tmp)
+                    copy_view(self.z_tmp[:c1], [self.zs[:c1, s * B:(s + 1) * B]])
+            copy_view(self.stage[self.n_eps:].view(self.F, self.N, nz), [self.zs[c1:]])
+        gen = self.gen.forward(self.images, self.zs, self.gt, actions=self.actions, states=self.states)
+        K.eval_fold_samples(eng.images_tm[eng.T - self.F:], gen, self.n_valid, self.st, self.ws)
+        return gen
+
+    def _run_chunk(self):
+        if not (self.use_graph and K.fused_ok()):
+            return self._chunk()
+
+        def body():
+            K.zero_arena(self.eng.device).reset()
+            return self._chunk()
+        if self.graph is not None:
+            self.graph.run()
+            return
+        if self.eager >= 1:                  # every conv problem of the S*B unroll tuned and every kernel loaded by the eager chunk
+            prog = _StepProgram(self.eng.device)
+            prog.capture(self.eng, body)
+            self.graph = prog
+            prog.run()
+            return
+        self.eager += 1
+        body()
+
+    def run(self, num_samples, noises):
+        if num_samples < 1:
+            raise ValueError('num_samples must be >= 1')
+        eng, dev = self.eng, self.eng.device
+        self._stage_batch()
+        flat, nv = self._host_draws(num_samples, noises)
+        flat, nv = flat.to(dev), nv.to(dev)
+        for c in range(flat.shape[0]):
+            self.stage.copy_(flat[c])
+            self.n_valid.copy_(nv[c:c + 1])
+            self._run_chunk()
+        outs, mets = OrderedDict(), OrderedDict()
+        outs['eval_images'] = eng.images_tm
+        inv = 1.0 / float(num_samples)
+        for k in SAVPEngine.METRICS:                  # (:215-221); fresh tensors, as the sequential path returns
+            a = {n: v.clone() for n, v in self.st[k].items()}
             K.axpby(inv, a['gsum'].reshape(-1), 0.0, a['gsum'].reshape(-1), a['gsum'].reshape(-1))
             K.axpby(inv, a['sum'].reshape(-1), 0.0, a['sum'].reshape(-1), a['sum'].reshape(-1))
             outs['eval_gen_images_%s/min' % k] = a['gmin']
@@ -1041,7 +1212,8 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         if inputs is not None:
             self.inputs = inputs
             self.engine.set_images(self.inputs)
-        self.eval_outputs, self.eval_metrics = self.engine.eval_outputs_and_metrics(num_samples or self.eval_num_samples, noises)
+        self.eval_outputs, self.eval_metrics = self.engine.eval_outputs_and_metrics(
+            num_samples or self.eval_num_samples, noises, parallel_iterations=parallel_iterations or self.eval_parallel_iterations)
         return self.eval_outputs, self.eval_metrics
 
     def restore(self, checkpoints, restore_to_checkpoint_mapping=None):
