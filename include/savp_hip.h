@@ -326,6 +326,23 @@ typedef struct SavpCdnaArgs {
 } SavpCdnaArgs;
 int savp_cdna_apply_fwd(void* stream, const SavpCdnaArgs* a);
 int savp_cdna_apply_bwd(void* stream, const SavpCdnaArgs* a);
+/* Multi-source forms (last_frames > 1, savp_model.py:926-952): the kernel tensor's nsrc*K columns are split into nsrc groups of K,
+ * group j is applied to img[j] and lands in out's channels [j*K*C, (j+1)*K*C).  One launch per call covers every source.
+ * bwd: dkern covers all nsrc*K columns (FLOAT64, overwritten); dimg[j] receives d(img[j]) (overwritten, or added to where
+ * dimg_beta[j] != 0; p NULL: not wanted).  The dimg[j] views must not overlap.  K <= 8, C <= 4, nsrc <= SAVP_MAX_SOURCES. */
+#define SAVP_MAX_SOURCES 4
+typedef struct SavpCdnaMultiArgs {
+    int32_t N, H, W, C, K, kh, kw; /* K: kernels per source */
+    int32_t nsrc;
+    SavpView img[SAVP_MAX_SOURCES];    /* [N,H,W,C] each, oldest frame first */
+    const float* kern;                 /* normalised kernels [N, kh*kw, nsrc*K] */
+    SavpView out;                      /* [N,H,W,nsrc*K*C], channel (j*K+k)*C+c */
+    SavpView dout;                     /* bwd: gradient of out */
+    SavpView dimg[SAVP_MAX_SOURCES]; int32_t dimg_beta[SAVP_MAX_SOURCES];
+    double* dkern;                     /* bwd: [N, kh*kw, nsrc*K] FLOAT64, overwritten; may be NULL */
+} SavpCdnaMultiArgs;
+int savp_cdna_apply_multi_fwd(void* stream, const SavpCdnaMultiArgs* a);
+int savp_cdna_apply_multi_bwd(void* stream, const SavpCdnaMultiArgs* a);
 typedef struct SavpCompositeArgs {
     int32_t N, HW, M, C;
     const float* logits;           /* [N*HW, logits_stride], first M columns are the mask logits */
@@ -490,6 +507,36 @@ typedef struct SavpDnaArgs {
 } SavpDnaArgs;
 int savp_dna_apply_fwd(void* stream, const SavpDnaArgs* a);
 int savp_dna_apply_bwd(void* stream, const SavpDnaArgs* a);
+/* Multi-source forms (last_frames > 1, savp_model.py:926-965), one launch per call for all sources: the nsrc*K flows / kernels are
+ * split into nsrc groups of K, group j is applied to img[j] and lands in out's channels [j*K*C, (j+1)*K*C).
+ * warp: flows / dflows [N,H,W,2*nsrc*K] (x components then y); dimg[j] any view, zeroed first where dimg_beta[j] == 0, then the
+ *       bilinear corners are added with atomics.  dna: raw / kern / draw [N,H*W,kh*kw*nsrc*K]; dimg[j] overwritten or added to
+ *       (dimg_beta[j]) in gather form.  dimg[j].p NULL: not wanted; the views must not overlap.  C <= 4, nsrc <= SAVP_MAX_SOURCES. */
+typedef struct SavpWarpMultiArgs {
+    int32_t N, H, W, C, K;             /* K: flows per source */
+    int32_t nsrc;
+    SavpView img[SAVP_MAX_SOURCES];
+    const float* flows;
+    SavpView out;
+    SavpView dout;
+    float* dflows;                     /* bwd: overwritten */
+    SavpView dimg[SAVP_MAX_SOURCES]; int32_t dimg_beta[SAVP_MAX_SOURCES];
+} SavpWarpMultiArgs;
+int savp_image_warp_multi_fwd(void* stream, const SavpWarpMultiArgs* a);
+int savp_image_warp_multi_bwd(void* stream, const SavpWarpMultiArgs* a);
+typedef struct SavpDnaMultiArgs {
+    int32_t N, H, W, C, K, kh, kw;     /* K: kernels per source */
+    int32_t nsrc;
+    SavpView img[SAVP_MAX_SOURCES];
+    const float* raw;
+    float* kern;
+    SavpView out;
+    SavpView dout;
+    float* draw;
+    SavpView dimg[SAVP_MAX_SOURCES]; int32_t dimg_beta[SAVP_MAX_SOURCES];
+} SavpDnaMultiArgs;
+int savp_dna_apply_multi_fwd(void* stream, const SavpDnaMultiArgs* a);
+int savp_dna_apply_multi_bwd(void* stream, const SavpDnaMultiArgs* a);
 
 /* ------------------------------------------------------------------------------------------------------------
  * gru.hip: fused gate blocks of Conv2DGRUCell (rnn_ops.py:234-267, instance norm, separate_norms=False).

@@ -101,22 +101,50 @@ __device__ __forceinline__ int sym(int q, int n) { return q < 0 ? -q - 1 : (q >=
 #define MAXK 8
 #define MAXC 4
 
-struct CdnaP {
-    int N, H, W, C, K, kh, kw, pt, pl;           // pt/pl = SAME pad before (kh-1)/2
+#define MAXS SAVP_MAX_SOURCES
+
+// one source image of a multi-source launch (last_frames > 1): its image view and where its image gradient goes
+struct CdnaSrc {
     const float* img; long long i_sn, i_sp;
-    const float* kern;                           // [N, kh*kw, K]
-    float* out; long long o_sn, o_sp;            // [N,H,W,K*C]  channel index k*C + c
+    float* dimg; long long di_sn, di_sp; int dimg_beta;
+};
+
+struct CdnaP {
+    int N, H, W, C, K, kh, kw, pt, pl;           // pt/pl = SAME pad before (kh-1)/2; K = kernels per source
+    int ks, koff;                                // kernel columns per tap in kern / dkern (nsrc*K) and the bound source's first one (j*K)
+    const float* img; long long i_sn, i_sp;      // the bound source (cdna_bind)
+    const float* kern;                           // [N, kh*kw, ks]; source j owns columns [j*K, (j+1)*K)
+    float* out; long long o_sn, o_sp;            // [N,H,W,ks*C]  channel index (koff+k)*C + c
     // bwd
     const float* dout; long long do_sn, do_sp;
     float* dimg; long long di_sn, di_sp; int dimg_beta;
-    double* dkern;                               // [N, kh*kw, K] float64 (overwritten): the tiles' partial sums meet here through float64 atomics -- exact, order-independent
+    double* dkern;                               // [N, kh*kw, ks] float64 (overwritten): the tiles' partial sums meet here through float64 atomics -- exact, order-independent
+    int nsrc; CdnaSrc src[MAXS];                 // source j = blockIdx.z; src[0] is what the fields above start with
 };
+
+// bind source blockIdx.z: image / gradient views and the column offset.  Static indices only (a runtime index into the kernel's
+// argument struct would spill it to scratch); blockIdx.z == 0 leaves the single-source launch exactly as it was.
+__device__ __forceinline__ void cdna_bind(CdnaP& p) {
+    const int j = blockIdx.z;
+#pragma unroll
+    for (int i = 1; i < MAXS; ++i)
+        if (i == j) {
+            p.img = p.src[i].img; p.i_sn = p.src[i].i_sn; p.i_sp = p.src[i].i_sp;
+            p.dimg = p.src[i].dimg; p.di_sn = p.src[i].di_sn; p.di_sp = p.src[i].di_sp; p.dimg_beta = p.src[i].dimg_beta;
+        }
+    p.koff = j * p.K;
+}
+// element i = tap * K + k of this source's [taps, K] kernel block of sample n
+__device__ __forceinline__ long long cdna_kidx(const CdnaP& p, int n, int taps, int i, int K) {
+    return ((long long)n * taps + i / K) * p.ks + p.koff + i % K;
+}
 
 __global__ __launch_bounds__(NT) void cdna_apply_fwd_kernel(CdnaP p) {
     __shared__ float sk[MAXTAPS * MAXK];
+    cdna_bind(p);
     const int n = blockIdx.y;
     const int taps = p.kh * p.kw;
-    for (int i = threadIdx.x; i < taps * p.K; i += NT) sk[i] = p.kern[(long long)n * taps * p.K + i];
+    for (int i = threadIdx.x; i < taps * p.K; i += NT) sk[i] = p.kern[cdna_kidx(p, n, taps, i, p.K)];
     __syncthreads();
     const int px = blockIdx.x * NT + threadIdx.x;
     if (px >= p.H * p.W) return;
@@ -145,7 +173,7 @@ __global__ __launch_bounds__(NT) void cdna_apply_fwd_kernel(CdnaP p) {
                 }
         }
     }
-    float* o = p.out + (long long)n * p.o_sn + (long long)px * p.o_sp;
+    float* o = p.out + (long long)n * p.o_sn + (long long)px * p.o_sp + p.koff * p.C;
     for (int k = 0; k < p.K; ++k)
         for (int c = 0; c < p.C; ++c) o[k * p.C + c] = acc[k][c];
 }
@@ -153,9 +181,11 @@ __global__ __launch_bounds__(NT) void cdna_apply_fwd_kernel(CdnaP p) {
 // d_img in gather form: every source pixel collects from the <=2x2 padded positions that mirror onto it.
 __global__ __launch_bounds__(NT) void cdna_apply_bwd_img_kernel(CdnaP p) {
     __shared__ float sk[MAXTAPS * MAXK];
+    cdna_bind(p);
+    if (!p.dimg) return;                         // (multi-source) this source's gradient is not wanted
     const int n = blockIdx.y;
     const int taps = p.kh * p.kw;
-    for (int i = threadIdx.x; i < taps * p.K; i += NT) sk[i] = p.kern[(long long)n * taps * p.K + i];
+    for (int i = threadIdx.x; i < taps * p.K; i += NT) sk[i] = p.kern[cdna_kidx(p, n, taps, i, p.K)];
     __syncthreads();
     const int px = blockIdx.x * NT + threadIdx.x;
     if (px >= p.H * p.W) return;
@@ -172,7 +202,7 @@ __global__ __launch_bounds__(NT) void cdna_apply_bwd_img_kernel(CdnaP p) {
     float acc[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) acc[c] = 0.f;
-    const float* dout = p.dout + (long long)n * p.do_sn;
+    const float* dout = p.dout + (long long)n * p.do_sn + p.koff * p.C;
     for (int a = 0; a < nqy; ++a)
         for (int b = 0; b < nqx; ++b) {
             // padded position (qy[a], qx[b]) is read by output (y, x) with tap (u, v): qy = y + u - pt
@@ -201,13 +231,14 @@ __global__ __launch_bounds__(NT) void cdna_apply_bwd_img_kernel(CdnaP p) {
 // for one (n,k) with per-thread tap accumulators.
 __global__ __launch_bounds__(NT) void cdna_apply_bwd_kern_kernel(CdnaP p) {
     __shared__ float sh[4 * MAXTAPS];
+    cdna_bind(p);
     const int k = blockIdx.x, n = blockIdx.y;
     const int taps = p.kh * p.kw;
     float acc[MAXTAPS];
 #pragma unroll
     for (int t = 0; t < MAXTAPS; ++t) acc[t] = 0.f;
     const float* im = p.img + (long long)n * p.i_sn;
-    const float* dout = p.dout + (long long)n * p.do_sn;
+    const float* dout = p.dout + (long long)n * p.do_sn + p.koff * p.C;
     for (int px = threadIdx.x; px < p.H * p.W; px += NT) {
         const int y = px / p.W, x = px % p.W;
         float d[MAXC];
@@ -237,7 +268,7 @@ __global__ __launch_bounds__(NT) void cdna_apply_bwd_kern_kernel(CdnaP p) {
     __syncthreads();
     if (threadIdx.x < taps) {
         const int t = threadIdx.x;
-        p.dkern[((long long)n * taps + t) * p.K + k] = (double)(sh[t] + sh[MAXTAPS + t] + sh[2 * MAXTAPS + t] + sh[3 * MAXTAPS + t]);
+        p.dkern[((long long)n * taps + t) * p.ks + p.koff + k] = (double)(sh[t] + sh[MAXTAPS + t] + sh[2 * MAXTAPS + t] + sh[3 * MAXTAPS + t]);
     }
 }
 
@@ -245,8 +276,10 @@ __global__ __launch_bounds__(NT) void cdna_apply_bwd_kern_kernel(CdnaP p) {
 template <int KH, int KW, int TK, int TC>
 __global__ __launch_bounds__(NT) void cdna_bwd_img_fast_kernel(CdnaP p) {
     __shared__ float sk[KH * KW * TK];
+    cdna_bind(p);
+    if (!p.dimg) return;
     const int n = blockIdx.y;
-    for (int i = threadIdx.x; i < KH * KW * TK; i += NT) sk[i] = p.kern[(long long)n * KH * KW * TK + i];
+    for (int i = threadIdx.x; i < KH * KW * TK; i += NT) sk[i] = p.kern[cdna_kidx(p, n, KH * KW, i, TK)];
     __syncthreads();
     const int px = blockIdx.x * NT + threadIdx.x;
     if (px >= p.H * p.W) return;
@@ -262,7 +295,7 @@ __global__ __launch_bounds__(NT) void cdna_bwd_img_fast_kernel(CdnaP p) {
     float acc[TC];
 #pragma unroll
     for (int c = 0; c < TC; ++c) acc[c] = 0.f;
-    const float* dout = p.dout + (long long)n * p.do_sn;
+    const float* dout = p.dout + (long long)n * p.do_sn + p.koff * TC;
     for (int a = 0; a < nqy; ++a)
         for (int b = 0; b < nqx; ++b) {
 #pragma unroll
@@ -304,13 +337,14 @@ template <int KH, int KW, int TK, int TC>
 __global__ __launch_bounds__(NT) void cdna_bwd_kern_fast_kernel(CdnaP p, int chunk) {
     constexpr int NV = KH * KW * TK;
     __shared__ float sh[4 * NV];
+    cdna_bind(p);
     const int n = blockIdx.y;
     constexpr int PT = (KH - 1) / 2, PL = (KW - 1) / 2;
     float acc[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) acc[i] = 0.f;
     const float* im = p.img + (long long)n * p.i_sn;
-    const float* dout = p.dout + (long long)n * p.do_sn;
+    const float* dout = p.dout + (long long)n * p.do_sn + p.koff * TC;
     const int p0 = blockIdx.x * chunk, p1 = min(p.H * p.W, p0 + chunk);
     for (int px = p0 + threadIdx.x; px < p1; px += NT) {
         const int y = px / p.W, x = px % p.W;
@@ -353,7 +387,7 @@ __global__ __launch_bounds__(NT) void cdna_bwd_kern_fast_kernel(CdnaP p, int chu
     }
     __syncthreads();
     for (int i = threadIdx.x; i < NV; i += NT)
-        unsafeAtomicAdd(p.dkern + (long long)n * NV + i, (double)(sh[i] + sh[NV + i] + sh[2 * NV + i] + sh[3 * NV + i]));
+        unsafeAtomicAdd(p.dkern + cdna_kidx(p, n, KH * KW, i, TK), (double)(sh[i] + sh[NV + i] + sh[2 * NV + i] + sh[3 * NV + i]));
 }
 
 // ---- LDS-tiled 5x5 kernels (compile-time K, C): a workgroup owns a 16x16 pixel tile --------------------------------------------
@@ -388,9 +422,10 @@ template <int TK, int TC>
 __global__ __launch_bounds__(NT) void cdna_apply_fwd_tiled_kernel(CdnaP p, int tiles_x, int vec) {
     __shared__ __attribute__((aligned(16))) float img[CT_HS * CT_HS * 4];
     __shared__ __attribute__((aligned(16))) float sk[25 * TK];
+    cdna_bind(p);
     const int n = blockIdx.y;
     const int ty0 = (blockIdx.x / tiles_x) * CT_TS, tx0 = (blockIdx.x % tiles_x) * CT_TS;
-    for (int i = threadIdx.x; i < 25 * TK; i += NT) sk[i] = p.kern[(long long)n * 25 * TK + i];
+    for (int i = threadIdx.x; i < 25 * TK; i += NT) sk[i] = p.kern[cdna_kidx(p, n, 25, i, TK)];
     stage_img_halo<TC>(p, n, ty0, tx0, img);
     __syncthreads();
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
@@ -414,7 +449,7 @@ __global__ __launch_bounds__(NT) void cdna_apply_fwd_tiled_kernel(CdnaP p, int t
                 for (int c = 0; c < TC; ++c) acc[k][c] += pix[c] * w;
             }
         }
-    float* o = p.out + (long long)n * p.o_sn + (long long)(y * p.W + x) * p.o_sp;
+    float* o = p.out + (long long)n * p.o_sn + (long long)(y * p.W + x) * p.o_sp + p.koff * TC;
     if (vec && (TK * TC) % 4 == 0) {
 #pragma unroll
         for (int q = 0; q < TK * TC / 4; ++q) {
@@ -435,7 +470,7 @@ __global__ __launch_bounds__(NT) void cdna_apply_fwd_tiled_kernel(CdnaP p, int t
 template <int TK, int TC>
 __device__ __forceinline__ void stage_dout_halo(const CdnaP& p, int n, int ty0, int tx0, int vec, float* dts) {
     constexpr int KC = TK * TC;
-    const float* dout = p.dout + (long long)n * p.do_sn;
+    const float* dout = p.dout + (long long)n * p.do_sn + p.koff * TC;
     for (int i = threadIdx.x; i < CT_HS * CT_HS; i += NT) {
         const int yy = i / CT_HS, xx = i - yy * CT_HS;
         const int y = ty0 + yy - 2, x = tx0 + xx - 2;
@@ -461,13 +496,15 @@ __global__ __launch_bounds__(NT) void cdna_bwd_img_tiled_kernel(CdnaP p, int til
     constexpr int KC = TK * TC, PT = 2, PL = 2, PB = 2, PR = 2;
     __shared__ __attribute__((aligned(16))) float dts[CT_HS * CT_HS * KC];
     __shared__ __attribute__((aligned(16))) float sk[25 * TK];
+    cdna_bind(p);
     const int n = blockIdx.y;
     const int ty0 = (blockIdx.x / tiles_x) * CT_TS, tx0 = (blockIdx.x % tiles_x) * CT_TS;
-    for (int i = threadIdx.x; i < 25 * TK; i += NT) sk[i] = p.kern[(long long)n * 25 * TK + i];
+    for (int i = threadIdx.x; i < 25 * TK; i += NT) sk[i] = p.kern[cdna_kidx(p, n, 25, i, TK)];
     // vec bit 1: clear this sample's kernel-gradient accumulator for the cdna_bwd_kern launch that follows on the stream (it
     // adds with atomics; saves the launcher a 12 KB memset per timestep)
     if ((vec & 2) && blockIdx.x == 0)
-        for (int i = threadIdx.x; i < 25 * TK; i += NT) p.dkern[(long long)n * 25 * TK + i] = 0.0;
+        for (int i = threadIdx.x; i < 25 * TK; i += NT) p.dkern[cdna_kidx(p, n, 25, i, TK)] = 0.0;
+    if (!p.dimg) return;                         // (multi-source) this source's gradient is not wanted; its dkern columns are cleared
     vec &= 1;
     stage_dout_halo<TK, TC>(p, n, ty0, tx0, vec, dts);
     __syncthreads();
@@ -531,6 +568,7 @@ __global__ __launch_bounds__(NT) void cdna_bwd_kern_tiled_kernel(CdnaP p, int ti
     constexpr int KC = TK * TC;
     __shared__ __attribute__((aligned(16))) float img[CT_HS * CT_HS * 4];
     __shared__ __attribute__((aligned(16))) float dts[NT * KC];
+    cdna_bind(p);
     const int n = blockIdx.y;
     const int ty0 = (blockIdx.x / tiles_x) * CT_TS, tx0 = (blockIdx.x % tiles_x) * CT_TS;
     const int lane = threadIdx.x & 63;
@@ -541,7 +579,7 @@ __global__ __launch_bounds__(NT) void cdna_bwd_kern_tiled_kernel(CdnaP p, int ti
     for (int t = 0; t < 7; ++t)
 #pragma unroll
         for (int k = 0; k < TK; ++k) acc[t][k] = 0.f;
-    const float* dout = p.dout + (long long)n * p.do_sn;
+    const float* dout = p.dout + (long long)n * p.do_sn + p.koff * TC;
     {
         const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
         const int y = ty0 + ty, x = tx0 + tx;
@@ -600,7 +638,7 @@ __global__ __launch_bounds__(NT) void cdna_bwd_kern_tiled_kernel(CdnaP p, int ti
 #pragma unroll
             for (int k = 0; k < TK; ++k) {
                 const float s = wsum(acc[t][k]);
-                if (lane == 0) unsafeAtomicAdd(p.dkern + ((long long)n * 25 + t_lo + t) * TK + k, (double)s);
+                if (lane == 0) unsafeAtomicAdd(p.dkern + ((long long)n * 25 + t_lo + t) * p.ks + p.koff + k, (double)s);
             }
         }
     }
@@ -610,70 +648,99 @@ static int fill_cdna(CdnaP& p, const SavpCdnaArgs* a) {
     if (!a || a->kh * a->kw > MAXTAPS || a->K > MAXK || a->C > MAXC || a->K < 1 || a->C < 1) return SAVP_EINVAL;
     p.N = a->N; p.H = a->H; p.W = a->W; p.C = a->C; p.K = a->K; p.kh = a->kh; p.kw = a->kw;
     p.pt = (a->kh - 1) / 2; p.pl = (a->kw - 1) / 2;
+    p.ks = a->K; p.koff = 0;
     p.img = (const float*)a->img.p; p.i_sn = a->img.sn; p.i_sp = a->img.sp;
     p.kern = a->kern;
     p.out = (float*)a->out.p; p.o_sn = a->out.sn; p.o_sp = a->out.sp;
     p.dout = (const float*)a->dout.p; p.do_sn = a->dout.sn; p.do_sp = a->dout.sp;
     p.dimg = (float*)a->dimg.p; p.di_sn = a->dimg.sn; p.di_sp = a->dimg.sp; p.dimg_beta = a->dimg_beta;
     p.dkern = (double*)a->dkern;
+    p.nsrc = 1;
+    p.src[0] = CdnaSrc{p.img, p.i_sn, p.i_sp, p.dimg, p.di_sn, p.di_sp, p.dimg_beta};
     if (p.dkern && (((uintptr_t)p.dkern) & 7)) return SAVP_EINVAL;
     return SAVP_OK;
+}
+
+static int fill_cdna_multi(CdnaP& p, const SavpCdnaMultiArgs* a) {
+    if (!a || a->nsrc < 1 || a->nsrc > MAXS || a->kh * a->kw > MAXTAPS || a->K > MAXK || a->C > MAXC || a->K < 1 || a->C < 1)
+        return SAVP_EINVAL;
+    p.N = a->N; p.H = a->H; p.W = a->W; p.C = a->C; p.K = a->K; p.kh = a->kh; p.kw = a->kw;
+    p.pt = (a->kh - 1) / 2; p.pl = (a->kw - 1) / 2;
+    p.ks = a->nsrc * a->K; p.koff = 0;
+    p.kern = a->kern;
+    p.out = (float*)a->out.p; p.o_sn = a->out.sn; p.o_sp = a->out.sp;
+    p.dout = (const float*)a->dout.p; p.do_sn = a->dout.sn; p.do_sp = a->dout.sp;
+    p.dkern = (double*)a->dkern;
+    p.nsrc = a->nsrc;
+    for (int j = 0; j < MAXS; ++j) {
+        const bool live = j < a->nsrc;
+        if (live && !a->img[j].p) return SAVP_EINVAL;
+        p.src[j] = live ? CdnaSrc{(const float*)a->img[j].p, a->img[j].sn, a->img[j].sp, (float*)a->dimg[j].p, a->dimg[j].sn, a->dimg[j].sp,
+                                  a->dimg_beta[j]}
+                        : CdnaSrc{nullptr, 0, 0, nullptr, 0, 0, 0};
+    }
+    p.img = p.src[0].img; p.i_sn = p.src[0].i_sn; p.i_sp = p.src[0].i_sp;
+    p.dimg = p.src[0].dimg; p.di_sn = p.src[0].di_sn; p.di_sp = p.src[0].di_sp; p.dimg_beta = p.src[0].dimg_beta;
+    if (p.dkern && (((uintptr_t)p.dkern) & 7)) return SAVP_EINVAL;
+    return SAVP_OK;
+}
+
+static bool cdna_any_dimg(const CdnaP& p) {
+    for (int j = 0; j < p.nsrc; ++j)
+        if (p.src[j].dimg) return true;
+    return false;
 }
 
 // SAVP_CDNA_LEGACY=1: the one-thread-per-pixel global-memory kernels (developer A/B switch)
 static bool cdna_legacy() {
     return savp_opt(OPT_CDNA_LEGACY) != 0;
 }
-// 3 / 1: the tiled 5x5, K = 4 kernels for C = 3 / 1 apply; 0: generic
-static int cdna_tiled_kind(const SavpCdnaArgs* a) {
-    if (cdna_legacy() || a->kh != 5 || a->kw != 5 || a->K != 4 || a->H < 3 || a->W < 3) return 0;
-    return a->C == 3 ? 3 : (a->C == 1 ? 1 : 0);
+// 3 / 1: the tiled 5x5, K = 4 kernels for C = 3 / 1 apply; 0: generic.  K is per source.
+static int cdna_tiled_kind(const CdnaP& p) {
+    if (cdna_legacy() || p.kh != 5 || p.kw != 5 || p.K != 4 || p.H < 3 || p.W < 3) return 0;
+    return p.C == 3 ? 3 : (p.C == 1 ? 1 : 0);
 }
 
-extern "C" int savp_cdna_apply_fwd(void* stream, const SavpCdnaArgs* a) {
-    CdnaP p;
-    int rc = fill_cdna(p, a);
-    if (rc) return rc;
-    const int kind = cdna_tiled_kind(a);
+// Every launch covers all sources (grid z); source j's channel / column offsets are multiples of K*C = 12 or 4 floats in the
+// vector paths, so the base pointer's alignment holds for each of them.
+static int cdna_fwd_launch(hipStream_t st, const CdnaP& p) {
+    const int kind = cdna_tiled_kind(p);
     if (kind) {
-        const int tiles_x = (a->W + CT_TS - 1) / CT_TS, tiles_y = (a->H + CT_TS - 1) / CT_TS;
-        const int vec = ((uintptr_t)a->out.p % 16 == 0) && (a->out.sn % 4 == 0) && (a->out.sp % 4 == 0);
-        dim3 grid(tiles_x * tiles_y, a->N);
-        if (kind == 3) hipLaunchKernelGGL((cdna_apply_fwd_tiled_kernel<4, 3>), grid, dim3(NT), 0, (hipStream_t)stream, p, tiles_x, vec);
-        else hipLaunchKernelGGL((cdna_apply_fwd_tiled_kernel<4, 1>), grid, dim3(NT), 0, (hipStream_t)stream, p, tiles_x, vec);
+        const int tiles_x = (p.W + CT_TS - 1) / CT_TS, tiles_y = (p.H + CT_TS - 1) / CT_TS;
+        const int vec = ((uintptr_t)p.out % 16 == 0) && (p.o_sn % 4 == 0) && (p.o_sp % 4 == 0);
+        dim3 grid(tiles_x * tiles_y, p.N, p.nsrc);
+        if (kind == 3) hipLaunchKernelGGL((cdna_apply_fwd_tiled_kernel<4, 3>), grid, dim3(NT), 0, st, p, tiles_x, vec);
+        else hipLaunchKernelGGL((cdna_apply_fwd_tiled_kernel<4, 1>), grid, dim3(NT), 0, st, p, tiles_x, vec);
         return LAUNCH_OK();
     }
-    hipLaunchKernelGGL(cdna_apply_fwd_kernel, dim3((a->H * a->W + NT - 1) / NT, a->N), dim3(NT), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(cdna_apply_fwd_kernel, dim3((p.H * p.W + NT - 1) / NT, p.N, p.nsrc), dim3(NT), 0, st, p);
     return LAUNCH_OK();
 }
 
-extern "C" int savp_cdna_apply_bwd(void* stream, const SavpCdnaArgs* a) {
-    CdnaP p;
-    int rc = fill_cdna(p, a);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const bool al = ((uintptr_t)a->dout.p % 16 == 0) && (a->dout.sn % 4 == 0) && (a->dout.sp % 4 == 0);
-    const int kind = cdna_tiled_kind(a);
+static int cdna_bwd_launch(hipStream_t st, const CdnaP& p) {
+    const bool al = ((uintptr_t)p.dout % 16 == 0) && (p.do_sn % 4 == 0) && (p.do_sp % 4 == 0);
+    const bool dimg = cdna_any_dimg(p);
+    const size_t dkern_bytes = (size_t)p.N * p.kh * p.kw * p.ks * sizeof(double);
+    const int kind = cdna_tiled_kind(p);
     if (kind) {
-        const int tiles_x = (a->W + CT_TS - 1) / CT_TS, tiles_y = (a->H + CT_TS - 1) / CT_TS;
+        const int tiles_x = (p.W + CT_TS - 1) / CT_TS, tiles_y = (p.H + CT_TS - 1) / CT_TS;
         const int vec = al ? 1 : 0;
-        if (p.dimg) {
-            dim3 grid(tiles_x * tiles_y, a->N);
+        dim3 grid(tiles_x * tiles_y, p.N, p.nsrc);
+        if (dimg) {
             const int v2 = vec | (p.dkern ? 2 : 0);
             if (kind == 3) hipLaunchKernelGGL((cdna_bwd_img_tiled_kernel<4, 3>), grid, dim3(NT), 0, st, p, tiles_x, v2);
             else hipLaunchKernelGGL((cdna_bwd_img_tiled_kernel<4, 1>), grid, dim3(NT), 0, st, p, tiles_x, v2);
         }
         if (p.dkern) {
-            if (!p.dimg) savp_zero_async(p.dkern, (size_t)a->N * 25 * 4 * sizeof(double), st);
-            dim3 grid(tiles_x * tiles_y, a->N);
+            if (!dimg) savp_zero_async(p.dkern, dkern_bytes, st);
             if (kind == 3) hipLaunchKernelGGL((cdna_bwd_kern_tiled_kernel<4, 3>), grid, dim3(NT), 0, st, p, tiles_x, vec);
             else hipLaunchKernelGGL((cdna_bwd_kern_tiled_kernel<4, 1>), grid, dim3(NT), 0, st, p, tiles_x, vec);
         }
         return LAUNCH_OK();
     }
-    const int fast = (a->kh == 5 && a->kw == 5 && a->K == 4 && a->C == 3 && al) ? 3 : ((a->kh == 5 && a->kw == 5 && a->K == 4 && a->C == 1 && al) ? 1 : 0);
-    dim3 gimg((a->H * a->W + NT - 1) / NT, a->N);
-    if (p.dimg) {
+    const int fast = (p.kh == 5 && p.kw == 5 && p.K == 4 && p.C == 3 && al) ? 3 : ((p.kh == 5 && p.kw == 5 && p.K == 4 && p.C == 1 && al) ? 1 : 0);
+    dim3 gimg((p.H * p.W + NT - 1) / NT, p.N, p.nsrc);
+    if (dimg) {
         if (fast == 3) hipLaunchKernelGGL((cdna_bwd_img_fast_kernel<5, 5, 4, 3>), gimg, dim3(NT), 0, st, p);
         else if (fast == 1) hipLaunchKernelGGL((cdna_bwd_img_fast_kernel<5, 5, 4, 1>), gimg, dim3(NT), 0, st, p);
         else hipLaunchKernelGGL(cdna_apply_bwd_img_kernel, gimg, dim3(NT), 0, st, p);
@@ -681,15 +748,43 @@ extern "C" int savp_cdna_apply_bwd(void* stream, const SavpCdnaArgs* a) {
     if (p.dkern) {
         if (fast) {
             const int chunk = 512;
-            savp_zero_async(p.dkern, (size_t)a->N * 25 * 4 * sizeof(double), st);
-            dim3 gk((a->H * a->W + chunk - 1) / chunk, a->N);
+            savp_zero_async(p.dkern, dkern_bytes, st);
+            dim3 gk((p.H * p.W + chunk - 1) / chunk, p.N, p.nsrc);
             if (fast == 3) hipLaunchKernelGGL((cdna_bwd_kern_fast_kernel<5, 5, 4, 3>), gk, dim3(NT), 0, st, p, chunk);
             else hipLaunchKernelGGL((cdna_bwd_kern_fast_kernel<5, 5, 4, 1>), gk, dim3(NT), 0, st, p, chunk);
         } else {
-            hipLaunchKernelGGL(cdna_apply_bwd_kern_kernel, dim3(a->K, a->N), dim3(NT), 0, st, p);
+            hipLaunchKernelGGL(cdna_apply_bwd_kern_kernel, dim3(p.K, p.N, p.nsrc), dim3(NT), 0, st, p);
         }
     }
     return LAUNCH_OK();
+}
+
+extern "C" int savp_cdna_apply_fwd(void* stream, const SavpCdnaArgs* a) {
+    CdnaP p;
+    int rc = fill_cdna(p, a);
+    if (rc) return rc;
+    return cdna_fwd_launch((hipStream_t)stream, p);
+}
+
+extern "C" int savp_cdna_apply_bwd(void* stream, const SavpCdnaArgs* a) {
+    CdnaP p;
+    int rc = fill_cdna(p, a);
+    if (rc) return rc;
+    return cdna_bwd_launch((hipStream_t)stream, p);
+}
+
+extern "C" int savp_cdna_apply_multi_fwd(void* stream, const SavpCdnaMultiArgs* a) {
+    CdnaP p;
+    int rc = fill_cdna_multi(p, a);
+    if (rc || !p.out) return rc ? rc : SAVP_EINVAL;
+    return cdna_fwd_launch((hipStream_t)stream, p);
+}
+
+extern "C" int savp_cdna_apply_multi_bwd(void* stream, const SavpCdnaMultiArgs* a) {
+    CdnaP p;
+    int rc = fill_cdna_multi(p, a);
+    if (rc || !p.dout) return rc ? rc : SAVP_EINVAL;
+    return cdna_bwd_launch((hipStream_t)stream, p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -957,6 +957,49 @@ def cdna_apply_bwd(img, kern, dout, dimg, dkern, kh, kw, K, dimg_beta=0):
     lib.check(_L().savp_cdna_apply_bwd(lib.stream(), ctypes.byref(a)), 'savp_cdna_apply_bwd')
 
 
+def _set_sources(a, imgs, dimgs=None, dimg_beta=0):
+    """Fill the per-source fields of a multi-source argument struct: imgs[j] [N,H,W,C] (oldest frame first), dimgs[j] its gradient
+    destination or None, dimg_beta an int for every source or one per source."""
+    if not 1 <= len(imgs) <= lib.MAX_SOURCES:
+        raise ValueError('1 .. %d source images, got %d' % (lib.MAX_SOURCES, len(imgs)))
+    if any(tuple(im.shape) != tuple(imgs[0].shape) for im in imgs):
+        raise ValueError('source images differ in shape: %s' % [tuple(im.shape) for im in imgs])
+    a.N, a.H, a.W, a.C = imgs[0].shape
+    a.nsrc = len(imgs)
+    for j, im in enumerate(imgs):
+        a.img[j] = view(im)
+    if dimgs is not None:
+        if len(dimgs) != len(imgs):
+            raise ValueError('one gradient destination (or None) per source image')
+        betas = dimg_beta if isinstance(dimg_beta, (list, tuple)) else [dimg_beta] * len(imgs)
+        for j, d in enumerate(dimgs):
+            if d is not None:
+                a.dimg[j] = view(d)
+            a.dimg_beta[j] = int(betas[j])
+    return a
+
+
+def cdna_apply_multi_fwd(imgs, kern, out, kh, kw, K):
+    """apply_kernels over last_frames sources (savp_model.py:926-952): kern [N, kh*kw, len(imgs)*K], group j applied to imgs[j],
+    written to out's channels [j*K*C, (j+1)*K*C)."""
+    a = _set_sources(lib.SavpCdnaMultiArgs(), imgs)
+    a.K, a.kh, a.kw = K, kh, kw
+    a.kern = _p(kern)
+    a.out = view(out)
+    lib.check(_L().savp_cdna_apply_multi_fwd(lib.stream(), ctypes.byref(a)), 'savp_cdna_apply_multi_fwd')
+
+
+def cdna_apply_multi_bwd(imgs, kern, dout, dimgs, dkern, kh, kw, K, dimg_beta=0):
+    """dkern: FLOAT64 [N, kh*kw, len(imgs)*K] (overwritten); dimgs[j] receives d imgs[j] (added to where its dimg_beta is 1)."""
+    a = _set_sources(lib.SavpCdnaMultiArgs(), imgs, dimgs, dimg_beta)
+    a.K, a.kh, a.kw = K, kh, kw
+    a.kern = _p(kern)
+    a.dout = view(dout)
+    lib.require_stats(dkern)
+    a.dkern = _p(dkern)
+    lib.check(_L().savp_cdna_apply_multi_bwd(lib.stream(), ctypes.byref(a)), 'savp_cdna_apply_multi_bwd')
+
+
 def _comp_args(logits, timgs, C, M):
     a = lib.SavpCompositeArgs()
     a.N, a.HW, a.M, a.C = logits.shape[0], _hw(logits), M, C
@@ -1274,6 +1317,29 @@ def image_warp_bwd(img, flows, dout, dflows, dimg, K_):
     lib.check(_L().savp_image_warp_bwd(lib.stream(), ctypes.byref(a)), 'savp_image_warp_bwd')
 
 
+def _warp_multi_args(imgs, flows, K_, dimgs=None, dimg_beta=0):
+    a = _set_sources(lib.SavpWarpMultiArgs(), imgs, dimgs, dimg_beta)
+    a.K = K_
+    assert flows.is_contiguous() and flows.shape[-1] == 2 * K_ * len(imgs)
+    a.flows = _p(flows)
+    return a
+
+
+def image_warp_multi_fwd(imgs, flows, out, K_):
+    """apply_flows over last_frames sources (savp_model.py:955-965): flows [N,H,W,2*len(imgs)*K_], group j warps imgs[j]."""
+    a = _warp_multi_args(imgs, flows, K_)
+    a.out = view(out)
+    lib.check(_L().savp_image_warp_multi_fwd(lib.stream(), ctypes.byref(a)), 'savp_image_warp_multi_fwd')
+
+
+def image_warp_multi_bwd(imgs, flows, dout, dflows, dimgs, K_, dimg_beta=0):
+    a = _warp_multi_args(imgs, flows, K_, dimgs, dimg_beta)
+    a.dout = view(dout)
+    assert dflows.is_contiguous()
+    a.dflows = _p(dflows)
+    lib.check(_L().savp_image_warp_multi_bwd(lib.stream(), ctypes.byref(a)), 'savp_image_warp_multi_bwd')
+
+
 def _dna_args(img, raw, kern, kh, kw, K_):
     a = lib.SavpDnaArgs()
     a.N, a.H, a.W, a.C = img.shape
@@ -1298,6 +1364,28 @@ def dna_apply_bwd(img, raw, kern, dout, draw, dimg, kh, kw, K_, dimg_beta=0):
         a.dimg = view(dimg)
     a.dimg_beta = int(dimg_beta)
     lib.check(_L().savp_dna_apply_bwd(lib.stream(), ctypes.byref(a)), 'savp_dna_apply_bwd')
+
+
+def _dna_multi_args(imgs, raw, kern, kh, kw, K_, dimgs=None, dimg_beta=0):
+    a = _set_sources(lib.SavpDnaMultiArgs(), imgs, dimgs, dimg_beta)
+    a.K, a.kh, a.kw = K_, kh, kw
+    assert raw.is_contiguous() and kern.is_contiguous()
+    a.raw, a.kern = _p(raw), _p(kern)
+    return a
+
+
+def dna_apply_multi_fwd(imgs, raw, kern, out, kh, kw, K_):
+    """per-pixel kernels over last_frames sources: raw / kern [N,H,W,kh*kw*len(imgs)*K_], group j applied to imgs[j]."""
+    a = _dna_multi_args(imgs, raw, kern, kh, kw, K_)
+    a.out = view(out)
+    lib.check(_L().savp_dna_apply_multi_fwd(lib.stream(), ctypes.byref(a)), 'savp_dna_apply_multi_fwd')
+
+
+def dna_apply_multi_bwd(imgs, raw, kern, dout, draw, dimgs, kh, kw, K_, dimg_beta=0):
+    a = _dna_multi_args(imgs, raw, kern, kh, kw, K_, dimgs, dimg_beta)
+    a.dout = view(dout)
+    a.draw = _p(draw)
+    lib.check(_L().savp_dna_apply_multi_bwd(lib.stream(), ctypes.byref(a)), 'savp_dna_apply_multi_bwd')
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -376,6 +376,35 @@ class SavpDnaArgs(ctypes.Structure):
                 ('dimg', SavpView), ('dimg_beta', c_i32)]
 
 
+MAX_SOURCES = 4      # SAVP_MAX_SOURCES: source images of one multi-source transformation call (last_frames)
+
+
+class SavpCdnaMultiArgs(ctypes.Structure):
+    _fields_ = [
+        ('N', c_i32), ('H', c_i32), ('W', c_i32), ('C', c_i32), ('K', c_i32), ('kh', c_i32), ('kw', c_i32), ('nsrc', c_i32),
+        ('img', SavpView * MAX_SOURCES), ('kern', c_vp), ('out', SavpView), ('dout', SavpView),
+        ('dimg', SavpView * MAX_SOURCES), ('dimg_beta', c_i32 * MAX_SOURCES), ('dkern', c_vp),
+    ]
+
+
+class SavpWarpMultiArgs(ctypes.Structure):
+    _fields_ = [('N', c_i32), ('H', c_i32), ('W', c_i32), ('C', c_i32), ('K', c_i32), ('nsrc', c_i32),
+                ('img', SavpView * MAX_SOURCES), ('flows', c_vp), ('out', SavpView), ('dout', SavpView), ('dflows', c_vp),
+                ('dimg', SavpView * MAX_SOURCES), ('dimg_beta', c_i32 * MAX_SOURCES)]
+
+
+class SavpDnaMultiArgs(ctypes.Structure):
+    _fields_ = [('N', c_i32), ('H', c_i32), ('W', c_i32), ('C', c_i32), ('K', c_i32), ('kh', c_i32), ('kw', c_i32), ('nsrc', c_i32),
+                ('img', SavpView * MAX_SOURCES), ('raw', c_vp), ('kern', c_vp), ('out', SavpView), ('dout', SavpView), ('draw', c_vp),
+                ('dimg', SavpView * MAX_SOURCES), ('dimg_beta', c_i32 * MAX_SOURCES)]
+
+
+register('savp_cdna_apply_multi_fwd', [c_vp, ctypes.POINTER(SavpCdnaMultiArgs)])
+register('savp_cdna_apply_multi_bwd', [c_vp, ctypes.POINTER(SavpCdnaMultiArgs)])
+register('savp_image_warp_multi_fwd', [c_vp, ctypes.POINTER(SavpWarpMultiArgs)])
+register('savp_image_warp_multi_bwd', [c_vp, ctypes.POINTER(SavpWarpMultiArgs)])
+register('savp_dna_apply_multi_fwd', [c_vp, ctypes.POINTER(SavpDnaMultiArgs)])
+register('savp_dna_apply_multi_bwd', [c_vp, ctypes.POINTER(SavpDnaMultiArgs)])
 register('savp_image_warp_fwd', [c_vp, ctypes.POINTER(SavpWarpArgs)])
 register('savp_image_warp_bwd', [c_vp, ctypes.POINTER(SavpWarpArgs)])
 register('savp_dna_apply_fwd', [c_vp, ctypes.POINTER(SavpDnaArgs)])

@@ -28,6 +28,12 @@ NORM_BWD_STATS = os.environ.get('SAVP_NORM_BWD_STATS', '1') == '1'      # ... an
 EPS_IN = 1e-6   # fused_instance_norm epsilon (layers/normalization.py:37)
 
 
+def last_frame_steps(t, L):
+    """The steps whose (scheduled-sampling selected) input images are step t's last_images, oldest first: the reference starts from
+    [images[0]] * L and appends each step's image (savp_model.py:281,349,406-407), so source j is step max(t - L + 1 + j, 0)."""
+    return [max(t - L + 1 + j, 0) for j in range(L)]
+
+
 def ceil4(n):
     return (n + 3) // 4 * 4
 
@@ -119,10 +125,25 @@ class SAVPGenerator(object):
             raise NotImplementedError('the normaliser-free cell is on the HIP path for conv_rnn = lstm only')
         if hp.downsample_layer != 'conv_pool2d' or hp.upsample_layer != 'upsample_conv2d' or hp.activation_layer != 'relu':
             raise NotImplementedError('HIP path covers conv_pool2d / upsample_conv2d / relu')
-        if hp.transformation not in ('cdna', 'flow', 'dna') or hp.last_frames != 1 or not hp.num_transformed_images:
-            raise NotImplementedError('HIP path covers transformation in (cdna, flow, dna) with last_frames=1')
-        if tuple(hp.dilation_rate) != (1, 1):
-            raise NotImplementedError('dilation_rate != (1, 1)')
+        if hp.transformation not in ('cdna', 'flow', 'dna') or hp.last_frames < 1 or not hp.num_transformed_images:
+            raise NotImplementedError('HIP path covers transformation in (cdna, flow, dna) with last_frames >= 1 and num_transformed_images >= 1')
+        # the multi-source transformation kernels (csrc/cdna_composite.hip, csrc/warp_dna.hip) take up to lib.MAX_SOURCES source frames
+        # of up to 8 CDNA kernels each; the compositing kernel up to 16 masks; the CDNA head's few-row dense kernel (savp_dense_fwd) up to
+        # 256 output columns
+        if hp.last_frames > lib.MAX_SOURCES:
+            raise NotImplementedError('last_frames = %d: the transformation kernels take at most %d source frames'
+                                      % (hp.last_frames, lib.MAX_SOURCES))
+        if hp.transformation == 'cdna' and hp.num_transformed_images > 8:
+            raise NotImplementedError('num_transformed_images = %d: at most 8 CDNA kernels per source frame' % hp.num_transformed_images)
+        ncol = hp.kernel_size[0] * hp.kernel_size[1] * hp.last_frames * hp.num_transformed_images
+        if hp.transformation == 'cdna' and ncol > 256:
+            raise NotImplementedError('CDNA head of %d columns (kernel taps x last_frames x num_transformed_images): the dense kernel takes '
+                                      'at most 256' % ncol)
+        if num_masks(hp) > 16:
+            raise NotImplementedError('%d masks (last_frames = %d): the compositing kernel takes at most 16' % (num_masks(hp), hp.last_frames))
+        # dilation_rate never reaches the transformations on SAVPCell: last_images is always a list, and the list branch of apply_kernels
+        # recurses as apply_kernels(image, kernels) without it (savp_model.py:939-944), so apply_cdna_kernels / apply_dna_kernels run
+        # with their default of (1, 1); nothing else in the cell reads it.  Any value computes what (1, 1) computes.
         if hp.nz and hp.use_rnn_z and hp.rnn not in ('lstm', 'gru') and not hp.ablation_rnn:
             raise NotImplementedError(hp.rnn)                                  # savp_model.py:360-361
         if hp.where_add not in ('input', 'all', 'middle'):
@@ -266,7 +287,9 @@ class SAVPGenerator(object):
         last = self.layers[-1]
         ngf = hp.ngf
         self.M = M = num_masks(hp)
+        self.L = hp.last_frames
         self.nk = nk = hp.last_frames * hp.num_transformed_images
+        self.nti = hp.num_transformed_images
         kh, kw = hp.kernel_size
         self.kh, self.kw = kh, kw
 
@@ -351,7 +374,10 @@ class SAVPGenerator(object):
         self.logits = Act((T1, N, H, W, Ml), dev, grad=g)
         self.masks = torch.empty(T1, N, H, W, M, device=dev)
         self.gen = Act((T1, N, H, W, C), dev, grad=g, zero_grad=True)
-        self.dimg_cdna = torch.empty(N, H, W, C, device=dev) if g else None
+        # gradient of the transformations' source image: one step's (last_frames = 1) or, for last_frames > 1, one accumulator per step
+        # (a generated frame is a source of up to last_frames later steps; BPTT adds their shares in a fixed order, see backward)
+        self.dimg_cdna = torch.empty(N, H, W, C, device=dev) if (g and self.L == 1) else None
+        self.dimg_acc = torch.empty(T1, N, H, W, C, device=dev) if (g and self.L > 1) else None
 
         # ---- actions / states (savp_model.py:411-422,655-658) -----------------------------------------------------
         # saz [T1, N, zw] = what every slice tiles: [actions_t | state_t | rnn_z_t]; the state recurrence (state_t = ground truth or the
@@ -652,19 +678,29 @@ class SAVPGenerator(object):
                        ([self.tf_h.v[t]] if self.tf != 'cdna' else [])
                 self._conv_norm('heads', self.heads_conv, self.h_last.v[t], self.heads_pre.v[t], hn, outs, t,
                                 out_ranges=[(i * ngf, ngf) for i in range(self.nheads)])
+            # last_frames > 1: the kernels / flows are split into L groups, group j applied to source j (apply_kernels / apply_flows,
+            # savp_model.py:926-965); the step's input buffers keep every selected image, so the sources are read where they are
+            srcs = [in0.v[s][..., 0:C] for s in last_frame_steps(t, self.L)] if self.L > 1 else None
             if self.tf == 'cdna':
                 # CDNA kernels from the smallest layer (savp_model.py:546-559) and their application (:580, :893-923)
                 self.cdna_dense.forward(self.hsmall.v[t].reshape(N, -1), self.cdna_raw.v[t])
                 K.cdna_kernels_fwd(self.cdna_raw.v[t], self.cdna_kern.v[t], self.kh, self.kw, self.nk)
-                K.cdna_apply_fwd(in0.v[t][..., 0:C], self.cdna_kern.v[t], tslot, self.kh, self.kw, self.nk)
+                if srcs is None:
+                    K.cdna_apply_fwd(in0.v[t][..., 0:C], self.cdna_kern.v[t], tslot, self.kh, self.kw, self.nk)
+                else:
+                    K.cdna_apply_multi_fwd(srcs, self.cdna_kern.v[t], tslot, self.kh, self.kw, self.nti)
             else:
                 if not self.merge_heads:
                     self._conv_norm('tf', self.tf_conv, self.h_last.v[t], self.tf_pre.v[t], self.tf_norm, [self.tf_h.v[t]], t)
                 self.tf_out.forward(self.tf_h.v[t], self.tf_raw.v[t])
-                if self.tf == 'flow':
+                if self.tf == 'flow' and srcs is None:
                     K.image_warp_fwd(in0.v[t][..., 0:C], self.tf_raw.v[t], tslot, self.nk)            # apply_flows :955-965
-                else:
+                elif self.tf == 'flow':
+                    K.image_warp_multi_fwd(srcs, self.tf_raw.v[t], tslot, self.nti)
+                elif srcs is None:
                     K.dna_apply_fwd(in0.v[t][..., 0:C], self.tf_raw.v[t], self.dna_kern[t], tslot, self.kh, self.kw, self.nk)
+                else:
+                    K.dna_apply_multi_fwd(srcs, self.tf_raw.v[t], self.dna_kern[t], tslot, self.kh, self.kw, self.nti)
             # scratch image (savp_model.py:561-572): sigmoid fused into the conv epilogue, written into its mask-conv slot
             if self.scratch and not self.merge_heads:
                 self._conv_norm('scratch', self.scratch_conv, self.h_last.v[t], self.scratch_pre.v[t], self.scratch_norm,
@@ -762,19 +798,37 @@ class SAVPGenerator(object):
                 self.scratch_out.backward_data(self.dscratch_pre[t], self.scratch_h.g[t], beta=0)
             # pixel transformation head (everything behind its 3x3 feature conv)
             dslot = maskin.g[t][..., self.o_cdna:self.o_cdna + self.nk * C]
+            if self.L > 1:
+                # source j is step tau = t - L + 1 + j; its gradient goes to that step's accumulator, read by step tau's select_bwd
+                # below once t has come down to tau.  Step tau's first share (from the latest step that reads it, where j == 0 or
+                # t == T1 - 1) overwrites, the later ones add.  tau <= 0 is dropped: step 0's image is a context frame.
+                steps = last_frame_steps(t, self.L)
+                srcs = [in0.v[s][..., 0:C] for s in steps]
+                taus = [t - self.L + 1 + j for j in range(self.L)]
+                dsrcs = [self.dimg_acc[tau] if tau > 0 else None for tau in taus]
+                betas = [0 if (j == 0 or t == T1 - 1) else 1 for j in range(self.L)]
             if self.tf == 'cdna':
-                K.cdna_apply_bwd(in0.v[t][..., 0:C], self.cdna_kern.v[t], dslot, self.dimg_cdna, self.cdna_dkern, self.kh,
-                                 self.kw, self.nk)
+                if self.L > 1:
+                    K.cdna_apply_multi_bwd(srcs, self.cdna_kern.v[t], dslot, dsrcs, self.cdna_dkern, self.kh, self.kw, self.nti, betas)
+                else:
+                    K.cdna_apply_bwd(in0.v[t][..., 0:C], self.cdna_kern.v[t], dslot, self.dimg_cdna, self.cdna_dkern, self.kh,
+                                     self.kw, self.nk)
                 K.cdna_kernels_bwd(self.cdna_raw.v[t], self.cdna_dkern, self.cdna_raw.g[t], self.kh, self.kw, self.nk)
                 self.cdna_dense.backward_data(self.cdna_raw.g[t], self.hsmall.g[t].reshape(N, -1), beta=0)
             else:
                 if self.tf == 'flow':
-                    K.image_warp_bwd(in0.v[t][..., 0:C], self.tf_raw.v[t], dslot, self.tf_raw.g[t], self.dimg_cdna, self.nk)
+                    if self.L > 1:
+                        K.image_warp_multi_bwd(srcs, self.tf_raw.v[t], dslot, self.tf_raw.g[t], dsrcs, self.nti, betas)
+                    else:
+                        K.image_warp_bwd(in0.v[t][..., 0:C], self.tf_raw.v[t], dslot, self.tf_raw.g[t], self.dimg_cdna, self.nk)
                     if self.tv is not None:          # total-variation loss of the flows (base_model.py:763-769): this step's share + gradient
                         w_tv, rows, acc = self.tv
                         s1 = 1.0 / (T1 * rows * (self.H - 1) * self.W)
                         s2 = 1.0 / (T1 * rows * self.H * (self.W - 1))
                         K.tv_loss(self.tf_raw.v[t][:rows], 2 * self.nk, s1, s2, w_tv, acc, self.tf_raw.g[t][:rows])
+                elif self.L > 1:
+                    K.dna_apply_multi_bwd(srcs, self.tf_raw.v[t], self.dna_kern[t], dslot, self.tf_raw.g[t], dsrcs, self.kh, self.kw,
+                                          self.nti, betas)
                 else:
                     K.dna_apply_bwd(in0.v[t][..., 0:C], self.tf_raw.v[t], self.dna_kern[t], dslot, self.tf_raw.g[t],
                                     self.dimg_cdna, self.kh, self.kw, self.nk)
@@ -887,7 +941,7 @@ class SAVPGenerator(object):
                 L['conv'].backward_data(L['pre'].g[t], L['in'].g[t], beta=0)
             # d image -> previous step's generated frame where it was fed back (not ground truth)
             if t > 0:
-                K.select_bwd(self.gt_mask[t], [in0.g[t][..., 0:C], self.dimg_cdna] +
+                K.select_bwd(self.gt_mask[t], [in0.g[t][..., 0:C], self.dimg_cdna if self.L == 1 else self.dimg_acc[t]] +
                              ([maskin.g[t][..., self.o_prev:self.o_prev + C]] if self.o_prev is not None else []), self.gen.g[t - 1])
         if self.learn_init:                # gradients of the learned initial states: step 0's state gradients summed over the batch
             for L in self.layers:
