@@ -612,7 +612,9 @@ int savp_eval_fold_samples(void* stream, const float* target, int64_t t_st, int6
 
 /* Fold float64 accumulators into fp32 gradients (round 6): dst[i] += (float) src[i] ; src[i] = 0 for i in idx[0 .. n) (idx NULL: i = 0 .. n-1).
  * The parameter gradients that many workgroups add to are accumulated in a float64 twin of the gradient arena (SavpInormArgs.dgamma, ...)
- * and rounded to fp32 once, here, before the optimiser (base_model.py:486-510) or the gradient exchange reads them. */
+ * and rounded to fp32 once, here, before the optimiser (base_model.py:486-510) or the gradient exchange reads them.  Elements whose
+ * accumulator is zero are skipped: neither dst[i] nor src[i] is accessed beyond reading src[i], so dst keeps its exact bits (a -0.0 or a
+ * NaN payload included) and a repeated fold stores nothing. */
 int savp_fold_f64(void* stream, const int32_t* idx, int64_t n, double* src, float* dst);
 
 /* The robot-state recurrence of the action / state-conditioned cell (savp_model.py:411-422, 655-658, 684-685), all T steps in one launch

@@ -55,7 +55,7 @@ struct GruP {
     int ndy; const float* dy[4]; long long dy_sn[4], dy_sp[4];
     float* dpre;                                         // [N,HW,F] or [N,HW,2F]
     float* du;                                           // output bwd: d u (post-sigmoid) [N,HW,F]; gates bwd reads it
-    float* dh; long long dh_sn, dh_sp;                   // accumulated (+=) gradient of h_prev
+    float* dh; long long dh_sn, dh_sp;                   // gradient of h_prev: out bwd overwrites it (u*dh'), gates bwd adds d(rh)*r
     const float* drh; long long drh_sn, drh_sp;          // gates bwd: gradient of the r*h slot
     double *dgamma, *dbeta;            // float64 accumulators (savp_hip.h SavpGruArgs)
 };
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(NT) void gru_out_fwd_kernel(GruP p) {
     }
 }
 
-// ---- output stage backward: dpre (candidate conv output), du, dh += u*dh' -------------------------------------------------
+// ---- output stage backward: dpre (candidate conv output), du, dh = u*dh' (overwritten) ---------------------------------------
 __global__ __launch_bounds__(NT) void gru_out_bwd_kernel(GruP p) {
     __shared__ float sh[4 * 8];
     const int cg = p.F / 4, n = blockIdx.x / cg, c0 = (blockIdx.x % cg) * 4, F = p.F;

@@ -306,7 +306,7 @@ extern "C" int savp_lstm_seq_bwd(void* stream, const float* A, const float* W, c
 //   [r, u] = sigmoid([x, h] Wg + bg) (r first);  c = tanh([x, r*h] Wc + bc);  h' = u*h + (1 - u)*c;  zero initial state.
 // A [T,B,I+U]: x_t in columns [0,I) (caller), h_{t-1} in [I,I+U) (written by fwd).  fwd also leaves A2 = [x | r*h_{t-1}] (the candidate
 // GEMM's input, needed for its weight gradient), ru [T,B,2U] (gate values), cand [T,B,U], hout [T,B,U].  One workgroup per batch row,
-// 2U threads.  bwd produces dGg [T,B,2U] / dGc [T,B,U] (gradients of the two pre-activations) and dA [T,B,I+U] (first I columns =
+// 2U threads (bwd: rounded up to whole waves).  bwd produces dGg [T,B,2U] / dGc [T,B,U] (gradients of the two pre-activations) and dA [T,B,I+U] (first I columns =
 // dL/dx); dWg = A^T dGg, dWc = A2^T dGc and the bias column sums are the caller's GEMMs (like savp_lstm_seq_*).
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void gru_seq_fwd_kernel(float* __restrict__ A, float* __restrict__ A2, const float* __restrict__ Wg, const float* __restrict__ bg,
@@ -366,7 +366,7 @@ __global__ void gru_seq_bwd_kernel(const float* __restrict__ A, const float* __r
     float* sh_dh = sh_drh + U;          // [U]  dL/dh_t carried from step t+1
     float* sh_dhp = sh_dh + U;          // [U]  direct part of dL/dh_{t-1}
     const int b = blockIdx.x, j = threadIdx.x;
-    const int lane = j & 63, wave = j >> 6, nwaves = (2 * U + 63) >> 6;
+    const int lane = j & 63, wave = j >> 6, nwaves = (2 * U + 63) >> 6;      // = blockDim.x / 64: whole waves (gru_bwd_threads)
     if (j < U) sh_dh[j] = 0.f;
     __syncthreads();
     for (int t = T - 1; t >= 0; --t) {
@@ -432,11 +432,16 @@ extern "C" int savp_gru_seq_fwd_init(void* stream, float* A, float* A2, const fl
     return LAUNCH_OK();
 }
 
+// The backward reduces each matrix row over one wave whose lanes stride the columns by 64, so every wave must be a whole one: with exactly
+// 2U threads and 2U > 64 not a multiple of 64 (U = 33, 40, 100, ...) the last wave has fewer lanes and its rows missed most columns.  The
+// launch is padded to whole waves; the kernel's per-unit work is guarded by j < U and its loops read columns < U / < 2U only.
+static inline int gru_bwd_threads(int U) { return ((2 * U + 63) / 64) * 64; }
+
 extern "C" int savp_gru_seq_bwd(void* stream, const float* A, const float* Wg, const float* Wc, const float* ru, const float* cand,
                                 const float* dh_out, float* dGg, float* dGc, float* dA, int32_t T, int32_t B, int32_t I, int32_t U) {
     if (!A || !Wg || !Wc || !ru || !cand || !dh_out || !dGg || !dGc || !dA || U < 1 || U > 512 || I < 1 || I + U > 4096) return SAVP_EINVAL;
-    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(B), dim3(2 * U), (size_t)(6 * U + I) * sizeof(float), (hipStream_t)stream, A, Wg, Wc, ru,
-                       cand, dh_out, dGg, dGc, dA, T, B, I, U, (double*)nullptr);
+    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(B), dim3(gru_bwd_threads(U)), (size_t)(6 * U + I) * sizeof(float), (hipStream_t)stream, A, Wg,
+                       Wc, ru, cand, dh_out, dGg, dGc, dA, T, B, I, U, (double*)nullptr);
     return LAUNCH_OK();
 }
 
@@ -444,8 +449,8 @@ extern "C" int savp_gru_seq_bwd_init(void* stream, const float* A, const float* 
                                      const float* dh_out, float* dGg, float* dGc, float* dA, int32_t T, int32_t B, int32_t I, int32_t U,
                                      double* dh0) {
     if (!A || !Wg || !Wc || !ru || !cand || !dh_out || !dGg || !dGc || !dA || !dh0 || U < 1 || U > 512 || I < 1 || I + U > 4096) return SAVP_EINVAL;
-    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(B), dim3(2 * U), (size_t)(6 * U + I) * sizeof(float), (hipStream_t)stream, A, Wg, Wc, ru,
-                       cand, dh_out, dGg, dGc, dA, T, B, I, U, dh0);
+    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(B), dim3(gru_bwd_threads(U)), (size_t)(6 * U + I) * sizeof(float), (hipStream_t)stream, A, Wg,
+                       Wc, ru, cand, dh_out, dGg, dGc, dA, T, B, I, U, dh0);
     return LAUNCH_OK();
 }
 
@@ -631,7 +636,7 @@ extern "C" int savp_tv_loss(void* stream, const float* flows, int32_t n_img, int
 }
 
 // GAN losses on logits [n] (losses.py:29-54).  type 0 LSGAN: mean((l-label)^2); 1 GAN: mean sigmoid cross-entropy with
-// constant labels; 2 SNGAN: mean softplus(l) for label 0, mean softplus(-l) for label 1.
+// constant labels 0 / 1; 2 SNGAN: mean softplus(l) for label 0, mean softplus(-l) for label 1.
 // loss_out += loss ; dlogits (=|+=) weight * dloss/dlogits
 __device__ __forceinline__ float softplus_(float x) { return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))); }
 __global__ void gan_loss_kernel(int n, int type, const float* logits, float label, float weight, double* loss_out, float* dlogits,
@@ -645,13 +650,12 @@ __global__ void gan_loss_kernel(int n, int type, const float* logits, float labe
             const float d = l - label;
             acc += d * d;
             g = 2.f * d;
-        } else if (type == 1) {
-            // max(l,0) - l*z + log(1+exp(-|l|))   (tf.nn.sigmoid_cross_entropy_with_logits)
-            acc += softplus_(l) - l * label;
-            g = 1.f / (1.f + __expf(-l)) - label;
         } else {
+            // GAN (tf.nn.sigmoid_cross_entropy_with_logits, max(l,0) - l*z + log(1+exp(-|l|))) and SNGAN coincide for the labels 0 / 1:
+            // softplus(l) resp. softplus(-l), gradient sigmoid(l) resp. -sigmoid(-l).  Written that way round, neither the value nor
+            // the gradient cancels for a large logit of the label's sign (softplus(30) - 30, sigmoid(30) - 1 are 0 in fp32)
             acc += (label == 0.f) ? softplus_(l) : softplus_(-l);
-            g = 1.f / (1.f + __expf(-l)) - ((label == 0.f) ? 0.f : 1.f);
+            g = (label == 0.f) ? 1.f / (1.f + __expf(-l)) : -1.f / (1.f + __expf(l));
         }
         if (dlogits) {
             g *= weight / (float)n;
@@ -665,7 +669,9 @@ __global__ void gan_loss_kernel(int n, int type, const float* logits, float labe
 extern "C" int savp_gan_loss(void* stream, int32_t n, int32_t type, const float* logits, float label, float weight, double* loss_out,
                              float* dlogits, int32_t beta) {
     if (!logits || n < 1 || type < 0 || type > 2) return SAVP_EINVAL;
-    if (type == 2 && label != 0.f && label != 1.f) return SAVP_EINVAL;
+    // GAN and SNGAN take the constant labels 0 / 1 only: for another label losses.py:34-37 subtracts the label's own entropy
+    // (sigmoid_kl_with_logits), which this kernel does not compute
+    if (type != 0 && label != 0.f && label != 1.f) return SAVP_EINVAL;
     hipLaunchKernelGGL(gan_loss_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, n, type, logits, label, weight, loss_out, dlogits,
                        beta);
     return LAUNCH_OK();

@@ -837,13 +837,18 @@ extern "C" int savp_u8_frames_to_f32(void* stream, const uint8_t* in, float* out
 // ---------------------------------------------------------------------------------------------------------------
 // Fold float64 accumulators into fp32 gradients (round 6): dst[i] += (float) src[i] ; src[i] = 0, for the elements listed in idx (NULL: the
 // first n elements).  The parameter gradients that many workgroups add to (norm gamma / beta, biases, the z-LSTM) are accumulated in a
-// float64 twin of the gradient arena -- exact, hence independent of arrival order -- and rounded to fp32 ONCE, here.
+// float64 twin of the gradient arena -- exact, hence independent of arrival order -- and rounded to fp32 ONCE, here.  A zero accumulator
+// is skipped: dst[i] is neither read nor written, so a fold that has nothing to add for an element (the second fold of a step, whose
+// elements the first one already cleared) does not store to a gradient another stream may be reducing meanwhile, and dst keeps its bits.
 __global__ __launch_bounds__(NT) void fold_f64_kernel(const int* __restrict__ idx, long long n, double* __restrict__ src, float* __restrict__ dst) {
     const long long t = (long long)blockIdx.x * NT + threadIdx.x;
     if (t >= n) return;
     const long long i = idx ? (long long)idx[t] : t;
-    dst[i] += (float)src[i];
-    src[i] = 0.0;
+    const double s = src[i];
+    if (s != 0.0) {
+        dst[i] += (float)s;
+        src[i] = 0.0;
+    }
 }
 
 extern "C" int savp_fold_f64(void* stream, const int32_t* idx, int64_t n, double* src, float* dst) {

@@ -562,7 +562,7 @@ def stats_ws(device, N, C):
     """An all-zero FLOAT64 [N, C, 2] reduction workspace from the step's zero arena: what conv(stats=...), the norm_bwd['ws'] epilogue and the
     coalesced instance-norm kernels accumulate their per-(sample, channel) sums in.  float64 because a sum of fp32 partials is exact there:
     the statistics do not depend on the order in which the workgroups' atomics arrive, so two runs of a step give the same bits."""
-    return zero_arena(device).take(N * C * 4).view(torch.float64).view(N, C, 2)
+    return zero_arena(device).take(N * C * 4)[:N * C * 4].view(torch.float64).view(N, C, 2)    # take() rounds up to 64 floats
 
 
 def _inorm_ws(x):
@@ -874,7 +874,8 @@ def fill_view(out, value=0.0):
 
 
 def fold64(src64, dst32, idx=None):
-    """dst32[i] += float(src64[i]); src64[i] = 0 for the elements listed in idx (int32 device tensor; None: all) -- ParamGroup.fold64."""
+    """dst32[i] += float(src64[i]); src64[i] = 0 for the elements listed in idx (int32 device tensor; None: all) whose accumulator is not
+    zero -- ParamGroup.fold64.  Elements with src64[i] == 0 are not touched."""
     lib.require_device(dst32)
     lib.require_stats(src64)
     if idx is not None:
