@@ -230,6 +230,57 @@ int savp_instnorm_act_fwd(void* stream, const SavpInormArgs* a);
 int savp_instnorm_act_bwd(void* stream, const SavpInormArgs* a);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Normalisation (+ ReLU / LeakyReLU) with statistics shared by G groups of C/G consecutive channels (group_norm.hip).
+ * G = 1 is tf.contrib.layers.layer_norm with its defaults (begin_norm_axis = 1, begin_params_axis = -1: mean and biased variance
+ * per sample over H, W and C, gamma / beta [C], eps 1e-12), the reference's norm_layer = 'layer' (ops.py:1062-1074; call sites
+ * savp_model.py:463-464,477,499-500,512,525,537,564,627, networks.py:26-27); G = C is the instance norm above.
+ * `norm` is read as for savp_instnorm_act_fwd / _bwd, except:
+ *   mean / rstd  [N][G] (fwd writes, bwd reads);
+ *   ws           REQUIRED, [N][C][2] float64 per-(sample, channel) sums: fwd with stats_ready = savp_conv's `stats` epilogue around
+ *                stats_shift (else a pass here fills them around the sample's first pixel); bwd with stats_ready = sum(dz), sum(dz * xhat)
+ *                per (sample, channel) with xhat of the GROUP statistics.  A fold launch combines them per (sample, group) in float64 with
+ *                the parallel-variance identity (fixed order: deterministic);
+ *   C % 4 == 0, C % G == 0, C / 4 <= 256 or a multiple of 256.
+ * bwd: dx = rstd * (gamma * dz - mean_g(gamma * dz) - xhat * mean_g(gamma * dz * xhat)), dz = sum_k dy[k] * act'; dgamma / dbeta as there.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct SavpGnormArgs {
+    SavpInormArgs norm;
+    int32_t G;                     /* groups (1 = layer norm) */
+    double* ws_group;              /* bwd: scratch [N][G][2] float64 (8-byte aligned; written before it is read) */
+    double* dsum;                  /* bwd, optional: FLOAT64 accumulator [C] += the sum of dx over samples and pixels -- the gradient of a
+                                      per-channel bias added in front of the norm (a layer norm, unlike an instance norm, does not remove it) */
+} SavpGnormArgs;
+int savp_groupnorm_act_fwd(void* stream, const SavpGnormArgs* a);
+int savp_groupnorm_act_bwd(void* stream, const SavpGnormArgs* a);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The pointwise parts of BasicConv2DLSTMCell with separate_norms = True (conv_rnn_norm_layer = 'layer', rnn_ops.py:147-165,
+ * savp_model.py:386-390; ln_lstm.hip).  The five layer norms are savp_groupnorm_act_* launches: G = 4 over the gate tensor
+ * (input / transform / forget / output, each over (H, W, F)) and G = 1 over the new state.
+ *   fwd stage 0: c_pre = c_prev * sigmoid(f + forget_bias) + sigmoid(i) * tanh(j)       (c_prev.p NULL: zero state)
+ *   fwd stage 1: h' = tanh(cn) * sigmoid(o) into nh destinations (bit k of h_bf16: destination k is bf16)
+ *   bwd stage 0: dcn = dc_new + dh * sigmoid(o) * (1 - tanh(cn)^2);  dgn[o] = dh * tanh(cn) * sigmoid'(o)   (dh = sum of ndh views)
+ *   bwd stage 1: dgn[i, j, f] from dc_pre;  dc_prev = dc_pre * sigmoid(f + forget_bias) (NULL: skipped)
+ * gn / dgn [N][HW][4F] (normalised gates i | j | f | o and their gradient), c_pre, cn, dc_new, dcn, dc_pre, dc_prev [N][HW][F]: contiguous fp32.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct SavpLnLstmArgs {
+    int32_t N, HW, F; float forget_bias;
+    const float* gn;
+    SavpView c_prev;
+    float* c_pre;
+    const float* cn;
+    int32_t nh; SavpView h[4]; int32_t h_bf16;
+    int32_t ndh; SavpView dh[4];
+    const float* dc_new;
+    float* dcn;
+    float* dgn;
+    const float* dc_pre;
+    float* dc_prev;
+} SavpLnLstmArgs;
+int savp_lnlstm_fwd(void* stream, const SavpLnLstmArgs* a, int32_t stage);
+int savp_lnlstm_bwd(void* stream, const SavpLnLstmArgs* a, int32_t stage);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Fused ConvLSTM gate block = everything in BasicConv2DLSTMCell.call after the convolution (rnn_ops.py:148-165,
  * normalizer fused_instance_norm, separate_norms=False, forget_bias 1.0):
  *   g = IN_{4F}(gates); i,j,f,o = split(g); c' = IN_F(c*sigmoid(f+fb) + sigmoid(i)*tanh(j)); h' = tanh(c')*sigmoid(o)

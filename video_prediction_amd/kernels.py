@@ -635,6 +635,122 @@ def instnorm_act_bwd(x, gamma, beta, out0, mean, rstd, dys, dx, dgamma, dbeta, d
     acc.finish()
 
 
+EPS_LN = 1e-12   # tf.contrib.layers.layer_norm's epsilon
+
+
+def groupnorm_act_fwd(x, gamma, beta, outs, mean, rstd, groups=1, act='relu', alpha=0.0, eps=EPS_LN, out_ranges=None, stats=None,
+                      stats_shift=None):
+    """savp_groupnorm_act_fwd: the statistics are shared by `groups` groups of C/groups consecutive channels (1 = layer norm);
+    mean / rstd are [N, groups].  Otherwise as instnorm_act_fwd (stats / stats_shift: the producing convolution's epilogue sums)."""
+    a = lib.SavpGnormArgs()
+    n = a.norm
+    if stats is not None:
+        lib.require_device(stats_shift)
+        lib.require_stats(stats)
+        n.ws, n.ws_clean, n.stats_ready = stats.data_ptr(), 1, 1
+        n.stats_shift = stats_shift.data_ptr() if stats_shift is not None else None
+    else:
+        n.ws, n.ws_clean = _inorm_ws(x).data_ptr(), 1
+    n.N, n.HW, n.C = x.shape[0], _hw(x), x.shape[-1]
+    n.act, n.alpha, n.eps = ACT_IDS[act], float(alpha), float(eps)
+    n.x = view(x)
+    n.gamma, n.beta = gamma.data_ptr(), beta.data_ptr()
+    n.nout = len(outs)
+    _set_views(n.out, outs, any_dtype=True)
+    n.out_bf16 = _bf16_mask(outs)
+    _set_ranges(n.out_c0, n.out_nc, out_ranges)
+    if mean.numel() != x.shape[0] * groups or rstd.numel() != x.shape[0] * groups:
+        raise ValueError('mean / rstd must hold N * groups values')
+    n.mean, n.rstd = mean.data_ptr(), rstd.data_ptr()
+    a.G = int(groups)
+    lib.check(lib.get().savp_groupnorm_act_fwd(lib.stream(), ctypes.byref(a)), 'savp_groupnorm_act_fwd')
+
+
+def groupnorm_act_bwd(x, gamma, beta, mean, rstd, dys, dx, dgamma, dbeta, groups=1, dx_beta=0, act='relu', alpha=0.0, eps=EPS_LN,
+                      dy_ranges=None, stats=None, dsum=None):
+    """savp_groupnorm_act_bwd.  dsum (optional, float64 [C], or float32 through a float64 twin): += the sum of dx over samples and
+    pixels, the gradient of a per-channel bias in front of the norm.  Otherwise as instnorm_act_bwd."""
+    a = lib.SavpGnormArgs()
+    n = a.norm
+    N, C = x.shape[0], x.shape[-1]
+    if stats is not None:
+        lib.require_stats(stats)
+        n.ws, n.ws_clean, n.stats_ready = stats.data_ptr(), 1, 1
+    else:
+        n.ws, n.ws_clean = _inorm_ws(x).data_ptr(), 1
+    n.N, n.HW, n.C = N, _hw(x), C
+    n.act, n.alpha, n.eps = ACT_IDS[act], float(alpha), float(eps)
+    n.x = view(x)
+    n.gamma, n.beta = gamma.data_ptr(), beta.data_ptr()
+    if mean.numel() != N * groups or rstd.numel() != N * groups:
+        raise ValueError('mean / rstd must hold N * groups values')
+    n.mean, n.rstd = mean.data_ptr(), rstd.data_ptr()
+    n.ndy = len(dys)
+    _set_views(n.dy, dys)
+    _set_ranges(n.dy_c0, n.dy_nc, dy_ranges)
+    n.dx = view(dx, any_dtype=True)
+    n.dx_bf16 = _bf16_mask([dx])
+    n.dx_beta = int(dx_beta)
+    acc = _Acc64(dgamma, dbeta, dsum)
+    n.dgamma, n.dbeta = acc.addr(0), acc.addr(1)
+    a.dsum = acc.addr(2)
+    a.G = int(groups)
+    a.ws_group = stats_ws(x.device, N, groups).data_ptr()
+    lib.check(lib.get().savp_groupnorm_act_bwd(lib.stream(), ctypes.byref(a)), 'savp_groupnorm_act_bwd')
+    acc.finish()
+
+
+def _lnlstm_args(gn, c_prev, forget_bias):
+    a = lib.SavpLnLstmArgs()
+    if not gn.is_contiguous() or gn.dtype != torch.float32:
+        raise ValueError('the normalised gates must be a contiguous float32 tensor')
+    a.N, a.HW, a.F = gn.shape[0], _hw(gn), gn.shape[-1] // 4
+    a.forget_bias = float(forget_bias)
+    a.gn = gn.data_ptr()
+    if c_prev is not None:
+        a.c_prev = view(c_prev)
+    return a
+
+
+def _contig(t):
+    if t is not None and (not t.is_contiguous() or t.dtype != torch.float32):
+        raise ValueError('expected a contiguous float32 tensor')
+    return t.data_ptr() if t is not None else None
+
+
+def lnlstm_state_fwd(gn, c_prev, c_pre, forget_bias=1.0):
+    """savp_lnlstm_fwd stage 0: c_pre = c_prev * sigmoid(f + fb) + sigmoid(i) * tanh(j) of the normalised gates gn [N, H, W, 4F]."""
+    a = _lnlstm_args(gn, c_prev, forget_bias)
+    a.c_pre = _contig(c_pre)
+    lib.check(lib.get().savp_lnlstm_fwd(lib.stream(), ctypes.byref(a), 0), 'savp_lnlstm_fwd')
+
+
+def lnlstm_out_fwd(gn, cn, hs):
+    """savp_lnlstm_fwd stage 1: h' = tanh(cn) * sigmoid(o) into every view of hs (fp32 or bf16)."""
+    a = _lnlstm_args(gn, None, 1.0)
+    a.cn = _contig(cn)
+    a.nh = len(hs)
+    _set_views(a.h, hs, any_dtype=True)
+    a.h_bf16 = _bf16_mask(hs)
+    lib.check(lib.get().savp_lnlstm_fwd(lib.stream(), ctypes.byref(a), 1), 'savp_lnlstm_fwd')
+
+
+def lnlstm_out_bwd(gn, cn, dhs, dc_new, dcn, dgn):
+    """savp_lnlstm_bwd stage 0: dcn = dc_new + dh * sigmoid(o) * tanh'(cn), dgn[..., 3F:4F] = dh * tanh(cn) * sigmoid'(o)."""
+    a = _lnlstm_args(gn, None, 1.0)
+    a.cn, a.dc_new, a.dcn, a.dgn = _contig(cn), _contig(dc_new), _contig(dcn), _contig(dgn)
+    a.ndh = len(dhs)
+    _set_views(a.dh, dhs)
+    lib.check(lib.get().savp_lnlstm_bwd(lib.stream(), ctypes.byref(a), 0), 'savp_lnlstm_bwd')
+
+
+def lnlstm_state_bwd(gn, c_prev, dc_pre, dgn, dc_prev, forget_bias=1.0):
+    """savp_lnlstm_bwd stage 1: dgn[..., 0:3F] from dc_pre; dc_prev = dc_pre * sigmoid(f + fb) (None: skipped)."""
+    a = _lnlstm_args(gn, c_prev, forget_bias)
+    a.dc_pre, a.dgn, a.dc_prev = _contig(dc_pre), _contig(dgn), _contig(dc_prev)
+    lib.check(lib.get().savp_lnlstm_bwd(lib.stream(), ctypes.byref(a), 1), 'savp_lnlstm_bwd')
+
+
 def _lstm_args(gates, c_prev, g1, b1, g2, b2, stats, eps, forget_bias):
     a = lib.SavpLstmArgs()
     N = gates.shape[0]

@@ -239,6 +239,18 @@ class SavpInormArgs(ctypes.Structure):
     ]
 
 
+class SavpGnormArgs(ctypes.Structure):
+    _fields_ = [('norm', SavpInormArgs), ('G', c_i32), ('ws_group', c_vp), ('dsum', c_vp)]
+
+
+class SavpLnLstmArgs(ctypes.Structure):
+    _fields_ = [
+        ('N', c_i32), ('HW', c_i32), ('F', c_i32), ('forget_bias', c_f32), ('gn', c_vp), ('c_prev', SavpView), ('c_pre', c_vp),
+        ('cn', c_vp), ('nh', c_i32), ('h', SavpView * 4), ('h_bf16', c_i32), ('ndh', c_i32), ('dh', SavpView * 4),
+        ('dc_new', c_vp), ('dcn', c_vp), ('dgn', c_vp), ('dc_pre', c_vp), ('dc_prev', c_vp),
+    ]
+
+
 class SavpLstmArgs(ctypes.Structure):
     _fields_ = [
         ('N', c_i32), ('HW', c_i32), ('F', c_i32), ('eps', c_f32), ('forget_bias', c_f32),
@@ -267,6 +279,10 @@ register('savp_conv_in_act_fwd', [c_vp, ctypes.POINTER(SavpConvNormArgs)])
 register('savp_conv_in_act_bwd', [c_vp, ctypes.POINTER(SavpConvNormArgs)])
 register('savp_instnorm_act_fwd', [c_vp, ctypes.POINTER(SavpInormArgs)])
 register('savp_instnorm_act_bwd', [c_vp, ctypes.POINTER(SavpInormArgs)])
+register('savp_groupnorm_act_fwd', [c_vp, ctypes.POINTER(SavpGnormArgs)])
+register('savp_groupnorm_act_bwd', [c_vp, ctypes.POINTER(SavpGnormArgs)])
+register('savp_lnlstm_fwd', [c_vp, ctypes.POINTER(SavpLnLstmArgs), c_i32])
+register('savp_lnlstm_bwd', [c_vp, ctypes.POINTER(SavpLnLstmArgs), c_i32])
 register('savp_convlstm_gates_fwd', [c_vp, ctypes.POINTER(SavpLstmArgs)])
 register('savp_convlstm_gates_bwd', [c_vp, ctypes.POINTER(SavpLstmArgs)])
 

@@ -10,7 +10,7 @@ import torch
 from .. import kernels as K
 from .. import lib
 from ..engine import ConvLayer, copy_view, prep_layers
-from ..variables import VIDEO_D_LAYERS, video_discriminator_shapes, image_discriminator_shapes
+from ..variables import NORM_SCOPES, VIDEO_D_LAYERS, video_discriminator_shapes, image_discriminator_shapes
 
 EPS_IN = 1e-6
 
@@ -37,8 +37,11 @@ class PosteriorEncoder(object):
         M, R = self.M, self.R
         dev = store.device
         self.dev = dev
-        if hp.norm_layer != 'instance':
-            raise NotImplementedError('HIP encoder covers norm_layer=instance')
+        if hp.norm_layer not in NORM_SCOPES:
+            raise NotImplementedError("HIP encoder covers norm_layer in ('instance', 'layer'), not %r" % hp.norm_layer)
+        # norm_layer = 'layer': tf.contrib.layers.layer_norm, statistics per sample (csrc/group_norm.hip with one group)
+        self.ln = hp.norm_layer == 'layer'
+        ns_ = NORM_SCOPES[hp.norm_layer]
         self.recurrent = bool(prior or hp.use_e_rnn)
         if self.recurrent and hp.rnn not in ('lstm', 'gru'):
             raise NotImplementedError(hp.rnn)                                  # savp_model.py:40-41
@@ -59,9 +62,10 @@ class PosteriorEncoder(object):
             if i > 0:
                 L['pre'] = torch.empty(max(M, 1), h, w, cout, device=dev)
                 L['dpre'] = torch.empty(max(M, 1), h, w, cout, device=dev) if train else None
-                L['gamma'], L['beta'] = store[s + 'InstanceNorm/gamma'], store[s + 'InstanceNorm/beta']
-                L['dgamma'], L['dbeta'] = store.grad64(s + 'InstanceNorm/gamma'), store.grad64(s + 'InstanceNorm/beta')   # float64 accumulators
-                L['mean'], L['rstd'] = torch.empty(max(M, 1), cout, device=dev), torch.empty(max(M, 1), cout, device=dev)
+                L['gamma'], L['beta'] = store[s + ns_ + 'gamma'], store[s + ns_ + 'beta']
+                L['dgamma'], L['dbeta'] = store.grad64(s + ns_ + 'gamma'), store.grad64(s + ns_ + 'beta')   # float64 accumulators
+                ms = 1 if self.ln else cout
+                L['mean'], L['rstd'] = torch.empty(max(M, 1), ms, device=dev), torch.empty(max(M, 1), ms, device=dev)
             self.layers.append(L)
             x = L['y']
             cin = cout
@@ -143,8 +147,12 @@ class PosteriorEncoder(object):
                     L['conv'].forward(L['x'], L['y'], act=lib.ACT_LRELU, alpha=0.2)            # networks.py:18-19
                 else:
                     L['conv'].forward(L['x'], L['pre'])
-                    K.instnorm_act_fwd(L['pre'], L['gamma'], L['beta'], [L['y']], L['mean'], L['rstd'], act='lrelu', alpha=0.2,
-                                       eps=EPS_IN)                                              # networks.py:25-27
+                    if self.ln:
+                        K.groupnorm_act_fwd(L['pre'], L['gamma'], L['beta'], [L['y']], L['mean'], L['rstd'], groups=1, act='lrelu',
+                                            alpha=0.2)
+                    else:
+                        K.instnorm_act_fwd(L['pre'], L['gamma'], L['beta'], [L['y']], L['mean'], L['rstd'], act='lrelu', alpha=0.2,
+                                           eps=EPS_IN)                                          # networks.py:25-27
             last = self.layers[-1]['y']
             self.pooled.zero_()
             K.colsum(last, self.pooled, scale=1.0 / self.hw, per_row=True)                     # networks.py:30-31
@@ -201,9 +209,13 @@ class PosteriorEncoder(object):
             K.tile_channels(self.dpooled, lastL['dy'], scale=1.0 / self.hw)
             for i in range(len(self.layers) - 1, -1, -1):
                 L = self.layers[i]
-                if L['normed']:
+                if L['normed'] and self.ln:
+                    K.groupnorm_act_bwd(L['pre'], L['gamma'], L['beta'], L['mean'], L['rstd'], [L['dy']], L['dpre'],
+                                        L['dgamma'], L['dbeta'], groups=1, act='lrelu', alpha=0.2)
+                if L['normed'] and not self.ln:
                     K.instnorm_act_bwd(L['pre'], L['gamma'], L['beta'], L['y'], L['mean'], L['rstd'], [L['dy']], L['dpre'],
                                        L['dgamma'], L['dbeta'], act='lrelu', alpha=0.2, eps=EPS_IN)
+                if L['normed']:
                     dpre = L['dpre']
                 else:
                     dpre = L['dy']       # already multiplied by lrelu' in the producing DGRAD epilogue

@@ -20,12 +20,31 @@ import torch
 from .. import kernels as K
 from .. import lib
 from ..engine import ConcatConv, ConvLayer, same_pad_before, copy_view, add_views, prep_layers
-from ..variables import layer_specs, num_masks
+from ..variables import NORM_SCOPES, layer_specs, num_masks
 
 CONV_STATS = os.environ.get('SAVP_CONV_STATS', '1') == '1'      # developer A/B switch of the conv-epilogue statistics
 FUSED_ENTRIES = os.environ.get('SAVP_FUSED_ENTRIES', '1') == '1'      # one host call per fused operator (csrc/fused_ops.hip); 0: the halves apart
 NORM_BWD_STATS = os.environ.get('SAVP_NORM_BWD_STATS', '1') == '1'      # ... and of the norm-backward sums from the DGRAD that produces dy
 EPS_IN = 1e-6   # fused_instance_norm epsilon (layers/normalization.py:37)
+
+
+def check_norm_layers(hp):
+    """The normaliser combinations of the HIP path; anything else raises with the combination named."""
+    if hp.conv_rnn not in ('lstm', 'gru'):
+        raise NotImplementedError("conv_rnn=%r" % hp.conv_rnn)
+    if hp.norm_layer not in ('instance', 'layer'):
+        raise NotImplementedError("norm_layer=%r: the HIP path covers 'instance' and 'layer'" % hp.norm_layer)
+    if hp.conv_rnn_norm_layer not in ('instance', 'layer', 'none'):
+        raise NotImplementedError("conv_rnn_norm_layer=%r: the HIP path covers 'instance', 'layer' and 'none'" % hp.conv_rnn_norm_layer)
+    layer = 'layer' in (hp.norm_layer, hp.conv_rnn_norm_layer)
+    if layer and not hp.use_tile_concat:
+        # the untiled latent (dense(z) added to a convolution's output) is dropped because an instance norm removes a per-(sample,
+        # channel) constant exactly; a layer norm removes only its mean over the channels, so the latent would matter
+        raise NotImplementedError("use_tile_concat=False with norm_layer=%r, conv_rnn_norm_layer=%r: the untiled latent is only "
+                                  "cancelled by an instance norm" % (hp.norm_layer, hp.conv_rnn_norm_layer))
+    if hp.conv_rnn_norm_layer == 'layer' and not hp.ablation_rnn:
+        if hp.conv_rnn == 'gru':
+            raise NotImplementedError("conv_rnn='gru' with conv_rnn_norm_layer='layer': the GRU gate kernels are instance-norm only")
 
 
 def last_frame_steps(t, L):
@@ -61,12 +80,39 @@ class Act(object):
 
 
 class Norm(object):
-    def __init__(self, store, scope, T1, N, C, device):
+    """Parameters and saved statistics of one normalizer_fn.  groups None: fused_instance_norm (mean / rstd per (sample, channel));
+    an integer: statistics shared by that many groups of consecutive channels (1 = tf.contrib.layers.layer_norm, mean / rstd
+    per sample; csrc/group_norm.hip)."""
+
+    def __init__(self, store, scope, T1, N, C, device, groups=None, bias=None):
         self.gamma, self.beta = store[scope + 'gamma'], store[scope + 'beta']
+        # a layer norm does not cancel the bias of the convolution in front of it: with a bf16 output gradient (which the bf16 WGRAD
+        # reads, and which takes no bias gradient) the norm's backward adds the column sums of its fp32 dx here (float64, exact)
+        self.dbias = store.grad64(bias) if (groups is not None and bias is not None) else None
         # float64 accumulators (ParamGroup.grad64): every (sample, channel slab) workgroup of a norm-backward launch adds to them
         self.dgamma, self.dbeta = store.grad64(scope + 'gamma'), store.grad64(scope + 'beta')
-        self.mean = torch.empty(T1, N, C, device=device)
-        self.rstd = torch.empty(T1, N, C, device=device)
+        self.groups = groups
+        self.mean = torch.empty(T1, N, C if groups is None else groups, device=device)
+        self.rstd = torch.empty(T1, N, C if groups is None else groups, device=device)
+
+
+def norm_fwd(nrm, x, outs, mean, rstd, act='relu', eps=EPS_IN, **kw):
+    """normalizer_fn + activation of `nrm`'s kind (the instance norm's own epsilon is the caller's; a layer norm always takes 1e-12)."""
+    if nrm.groups is None:
+        K.instnorm_act_fwd(x, nrm.gamma, nrm.beta, outs, mean, rstd, act=act, eps=eps, **kw)
+    else:
+        K.groupnorm_act_fwd(x, nrm.gamma, nrm.beta, outs, mean, rstd, groups=nrm.groups, act=act, eps=K.EPS_LN, **kw)
+
+
+def norm_bwd(nrm, x, out0, mean, rstd, dys, dx, dgamma, dbeta, act='relu', eps=EPS_IN, stats=None, **kw):
+    """Backward of norm_fwd (out0 is not read)."""
+    if nrm.groups is None:
+        K.instnorm_act_bwd(x, nrm.gamma, nrm.beta, out0, mean, rstd, dys, dx, dgamma, dbeta, act=act, eps=eps, stats=stats, **kw)
+    else:
+        assert stats is None, 'the layer norm takes its own backward sums'
+        dsum = nrm.dbias if dx.dtype == torch.bfloat16 else None       # an fp32 dx: the convolution's WGRAD takes the bias gradient itself
+        K.groupnorm_act_bwd(x, nrm.gamma, nrm.beta, mean, rstd, dys, dx, dgamma, dbeta, groups=nrm.groups, act=act, eps=K.EPS_LN,
+                            dsum=dsum, **kw)
 
 
 class ConcatNorm(object):
@@ -80,8 +126,15 @@ class ConcatNorm(object):
         C = sum(self.sizes)
         self.gamma, self.beta = torch.empty(C, device=device), torch.empty(C, device=device)
         self.dgamma, self.dbeta = torch.zeros(C, device=device, dtype=torch.float64), torch.zeros(C, device=device, dtype=torch.float64)
-        self.mean = torch.empty(T1, N, C, device=device)
-        self.rstd = torch.empty(T1, N, C, device=device)
+        # layer norms: one group per head (equal widths), so the heads keep their own statistics
+        self.groups = None if norms[0].groups is None else len(norms)
+        if self.groups is not None and len(set(self.sizes)) != 1:
+            raise NotImplementedError('layer-normalised heads of different widths')
+        self.mean = torch.empty(T1, N, C if self.groups is None else self.groups, device=device)
+        self.rstd = torch.empty(T1, N, C if self.groups is None else self.groups, device=device)
+        self.dbias = None
+        if self.groups is not None and all(n.dbias is not None for n in norms):
+            self.dbias = torch.zeros(C, device=device, dtype=torch.float64)
 
     def prep(self):
         off = 0
@@ -95,9 +148,13 @@ class ConcatNorm(object):
         for n, c in zip(self.norms, self.sizes):
             n.dgamma.add_(self.dgamma[off:off + c])          # float64 accumulators on both sides
             n.dbeta.add_(self.dbeta[off:off + c])
+            if self.dbias is not None:
+                n.dbias.add_(self.dbias[off:off + c])
             off += c
         self.dgamma.zero_()
         self.dbeta.zero_()
+        if self.dbias is not None:
+            self.dbias.zero_()
 
 
 class SAVPGenerator(object):
@@ -112,8 +169,13 @@ class SAVPGenerator(object):
         dev = store.device
         self.dev = dev
         self._cstats = {}                # head name -> the conv's epilogue supplies the instance norm's statistics (decided at first use)
-        if hp.conv_rnn not in ('lstm', 'gru') or hp.conv_rnn_norm_layer not in ('instance', 'none') or hp.norm_layer != 'instance':
-            raise NotImplementedError('HIP path covers conv_rnn in (lstm, gru) with instance norm (or no normaliser inside the LSTM cell)')
+        check_norm_layers(hp)
+        # norm_layer = 'layer': every norm_layer site (the ladder's layers, ablation_rnn's conv_h<i>, the 3x3 heads) is a layer norm,
+        # variables under <scope>/LayerNorm/ (csrc/group_norm.hip with one group; the heads' merged launch: one group per head)
+        self.ln = hp.norm_layer == 'layer'
+        # conv_rnn_norm_layer = 'layer' inside the ConvLSTM cell (separate_norms, rnn_ops.py:147-165): the gate convolution (no bias),
+        # a layer norm per gate (one G = 4 launch), the pointwise state update, a layer norm of the new state, h' (csrc/ln_lstm.hip)
+        self.cell_ln = bool(hp.conv_rnn_norm_layer == 'layer' and not hp.ablation_conv_rnn_norm)
         # The ConvLSTM cell WITHOUT a normaliser (rnn_ops.py:122-125: the gate convolution then has a bias; :148-165 with normalizer_fn None):
         # conv_rnn_norm_layer = 'none', or ablation_conv_rnn_norm (savp_model.py:380-384: the cell is built without one and the layer's OUTPUT
         # h -- not the state handed to the next step -- goes through normalizer_fn, variables under <cell scope>/InstanceNorm/).
@@ -220,13 +282,13 @@ class SAVPGenerator(object):
             #  the bf16-operand kernel)
             pre16 = f % 8 == 0 and (i < self.ne or L['in'].v.dtype == torch.bfloat16 or not self.act16)
             L['pre'] = Act((T1, N, h_, w_, f), dev, grad=g, grad_dtype=a16 if pre16 else torch.float32)
-            L['norm'] = Norm(store, s + 'InstanceNorm/', T1, N, f, dev)
+            L['norm'] = self._norm(s, f, bias=L['conv'].bias_name)
             if use_rnn and self.abl_rnn:
                 r = prefix + 'conv_h%d/' % i
                 L['a'] = Act((T1, N, h_, w_, ceil4(f + zr)), dev, grad=g, dtype=a16 if ceil4(f + zr) % 8 == 0 else torch.float32)
                 L['pre2'] = Act((T1, N, h_, w_, f), dev, grad=g, grad_dtype=a16 if f % 8 == 0 else torch.float32)
                 L['rconv'] = ConvLayer(store, r + 'conv2d/kernel', r + 'conv2d/bias', 'conv', (5, 5), (1, 1), (2, 2), cx_pad=ceil4(f + zr))
-                L['n2'] = Norm(store, r + 'InstanceNorm/', T1, N, f, dev)
+                L['n2'] = self._norm(r, f, bias=r + 'conv2d/bias')
             elif use_rnn and hp.conv_rnn == 'gru':
                 # Conv2DGRUCell (rnn_ops.py:174-267): a = [x | z | h_prev | r*h_prev]; the gates conv reads the first
                 # f+zc+f channels of the same buffer (a channel-slice view), the candidate conv reads all of it
@@ -247,6 +309,7 @@ class SAVPGenerator(object):
                 # fused ConvLSTM cell of the bf16 datapath: the gate convolution's epilogue produces the statistics of the first
                 # instance norm and stores the gate pre-activations as bf16 (csrc/conv_ring.hip) -> conv + 2 launches per cell
                 L['fused'] = (K.PRECISION['value'] == 1 and os.environ.get('SAVP_FUSED_CELL', '1') == '1' and not self.cell_plain and
+                              not self.cell_ln and
                               h_ % 8 == 0 and w_ % 8 == 0 and 16 <= f <= 256 and (f & (f - 1)) == 0 and (f + zr + f) % 8 == 0)
                 # The cell's input buffer [x | z | h] and the gate gradient are held in bf16 (round 3: validated on MI355X, identical
                 # numbers -- their only readers are the gate convolution's FPROP / DGRAD / WGRAD, which round to bf16 when they stage
@@ -262,16 +325,24 @@ class SAVPGenerator(object):
                 L['c'] = Act((T1, N, h_, w_, f), dev, grad=False)
                 L['dc'] = [torch.empty(N, h_, w_, f, device=dev), torch.empty(N, h_, w_, f, device=dev)] if g else None
                 L['rconv'] = ConvLayer(store, r + 'kernel', (r + 'bias') if self.cell_plain else None, 'conv', (5, 5), (1, 1), (2, 2))
-                if not self.cell_plain:
+                if not self.cell_plain and not self.cell_ln:
                     # the gate convolution's own kernel (bf16 datapath, csrc/conv_gate.hip); where a tile holds whole images (planes of <= 256
                     # pixels) also the interleaved pack: savp_convlstm_cell_fwd then runs the whole cell forward as one launch
                     L['rconv'].enable_gate_pack(cell=bool(L['fused']) and h_ * w_ <= 256)
-                if not self.cell_plain:
+                if self.cell_ln:
+                    # input / transform / forget / output: one G = 4 launch over the gate tensor, parameters gathered per step
+                    L['gn4'] = ConcatNorm([Norm(store, r + nm + '/', T1, N, f, dev, groups=1) for nm in ('input', 'transform', 'forget', 'output')],
+                                          T1, N, dev)
+                    L['nS'] = Norm(store, r + 'state/', T1, N, f, dev, groups=1)
+                    L['gnv'] = Act((T1, N, h_, w_, 4 * f), dev, grad=g)          # the normalised gates and their gradient
+                    L['cpre'] = Act((T1, N, h_, w_, f), dev, grad=g)             # the state before its norm
+                    L['dcn'] = torch.empty(N, h_, w_, f, device=dev) if g else None
+                elif not self.cell_plain:
                     L['n1'] = Norm(store, r + 'input_transform_forget_output/', T1, N, 4 * f, dev)
                     L['n2'] = Norm(store, r + 'state/', T1, N, f, dev)
                 if self.out_norm:
                     L['h_raw'] = Act((T1, N, h_, w_, f), dev, grad=g)
-                    L['onorm'] = Norm(store, prefix + 'lstm_h%d/InstanceNorm/' % i, T1, N, f, dev)
+                    L['onorm'] = self._norm(prefix + 'lstm_h%d/' % i, f, hp.conv_rnn_norm_layer)
                 # The data gradient of the gate convolution leaves the tiled-z channels of [x | z | h] out (their gradient is a per-sample
                 # sum, taken once over all timesteps from region sums of the gate gradient: csrc/tiled_z.hip), which keeps its column count
                 # on a tile boundary (72 / 136 / 264 -> 64 / 128 / 256; KTH's nz = 32: 96 / 160 / 288 -> 64 / 128 / 256).  bf16 datapath (the ring kernel owns the column gap).
@@ -317,7 +388,7 @@ class SAVPGenerator(object):
             s = prefix + hs
             self.tf_conv = ConvLayer(store, s + 'conv2d/kernel', s + 'conv2d/bias', 'conv', (3, 3), (1, 1), (1, 1))
             self.tf_pre = Act((T1, N, H, W, ngf), dev, grad=g)
-            self.tf_norm = Norm(store, s + 'InstanceNorm/', T1, N, ngf, dev)
+            self.tf_norm = self._norm(s, ngf, bias=s + 'conv2d/bias')
             self.tf_h = Act((T1, N, H, W, ngf), dev, grad=g)
             self.tf_out = ConvLayer(store, prefix + os_ + 'conv2d/kernel', prefix + os_ + 'conv2d/bias', 'conv', (3, 3), (1, 1),
                                     (1, 1), cy_pad=ceil4(cy))
@@ -337,7 +408,7 @@ class SAVPGenerator(object):
             s = prefix + 'h%d_scratch/' % nl
             self.scratch_conv = ConvLayer(store, s + 'conv2d/kernel', s + 'conv2d/bias', 'conv', (3, 3), (1, 1), (1, 1))
             self.scratch_pre = Act((T1, N, H, W, ngf), dev, grad=g) if sep else None
-            self.scratch_norm = Norm(store, s + 'InstanceNorm/', T1, N, ngf, dev)
+            self.scratch_norm = self._norm(s, ngf, bias=s + 'conv2d/bias')
             self.scratch_h = Act((T1, N, H, W, ngf), dev, grad=g)
             s = prefix + 'scratch_image/'
             self.scratch_out = ConvLayer(store, s + 'conv2d/kernel', s + 'conv2d/bias', 'conv', (3, 3), (1, 1), (1, 1), cy_pad=Cs)
@@ -345,7 +416,7 @@ class SAVPGenerator(object):
         s = prefix + 'h%d_masks/' % nl
         self.masks_conv = ConvLayer(store, s + 'conv2d/kernel', s + 'conv2d/bias', 'conv', (3, 3), (1, 1), (1, 1))
         self.masks_pre = Act((T1, N, H, W, ngf), dev, grad=g) if sep else None
-        self.masks_norm = Norm(store, s + 'InstanceNorm/', T1, N, ngf, dev)
+        self.masks_norm = self._norm(s, ngf, bias=s + 'conv2d/bias')
         # background images in the reference's order (savp_model.py:581-594): the step's input image, then frames of the INPUT video --
         # ('fixed', k) = images[k] at every step, ('last_context',) = images[min(t, context_frames - 1)]
         cf = hp.context_frames
@@ -460,7 +531,8 @@ class SAVPGenerator(object):
             self.nheads = len(parts)
             self.heads_conv = ConcatConv(store, parts, (3, 3), (1, 1), (1, 1))
             self.heads_norm = ConcatNorm(norms, T1, N, dev)
-            self.heads_pre = Act((T1, N, H, W, self.nheads * ngf), dev, grad=g, grad_dtype=a16 if (self.nheads * ngf) % 8 == 0 else torch.float32)
+            self.heads_pre = Act((T1, N, H, W, self.nheads * ngf), dev, grad=g,
+                                 grad_dtype=a16 if (self.nheads * ngf) % 8 == 0 else torch.float32)
             head_convs = [self.heads_conv]
         self.convs = [L['conv'] for L in self.layers] + [L['rconv'] for L in self.layers if L['rnn']] + \
                      [L['cconv'] for L in self.layers if L['rnn'] and self.gru and not self.abl_rnn] + \
@@ -496,6 +568,9 @@ class SAVPGenerator(object):
         prep_layers(self.convs)
         if self.merge_heads:
             self.heads_norm.prep()
+        for L in self.layers:
+            if 'gn4' in L:
+                L['gn4'].prep()
 
     # ---------------------------------------------------------------------------------------------------------
     def _out_views(self, L, t):
@@ -608,8 +683,8 @@ class SAVPGenerator(object):
                     L['conv'].forward(L['in'].v[t], L['pre'].v[t], stats=st)
                     a = L['a']
                     hs, rs_, cin1 = f + L['zr'], f + L['zr'] + f, L['cin1']
-                    K.instnorm_act_fwd(L['pre'].v[t], nrm.gamma, nrm.beta, [a.v[t][..., 0:f]], nrm.mean[t], nrm.rstd[t],
-                                       act='relu', eps=EPS_IN, stats=st, stats_shift=L['conv'].bias if st is not None else None)
+                    norm_fwd(nrm, L['pre'].v[t], [a.v[t][..., 0:f]], nrm.mean[t], nrm.rstd[t],
+                             act='relu', eps=EPS_IN, stats=st, stats_shift=L['conv'].bias if st is not None else None)
                     n1, n2 = L['n1'], L['n2']
                     hprev = a.v[t][..., hs:hs + f]
                     L['rconv'].forward(a.v[t][..., 0:cin1], L['gates'].v[t], use_bias=False)
@@ -629,7 +704,18 @@ class SAVPGenerator(object):
                     K.convlstm_gates_fwd(L['gates'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), None, None, None, None, L['c'].v[t], hdst, None)
                     if self.out_norm:
                         on = L['onorm']
-                        K.instnorm_act_fwd(L['h_raw'].v[t], on.gamma, on.beta, self._out_views(L, t), on.mean[t], on.rstd[t], act='none', eps=EPS_IN)
+                        norm_fwd(on, L['h_raw'].v[t], self._out_views(L, t), on.mean[t], on.rstd[t], act='none', eps=EPS_IN)
+                elif L['rnn'] and self.cell_ln:
+                    a, g4, nS = L['a'], L['gn4'], L['nS']
+                    self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, [a.v[t][..., 0:f]], t)
+                    L['rconv'].forward(a.v[t], L['gates'].v[t], use_bias=False)
+                    K.groupnorm_act_fwd(L['gates'].v[t], g4.gamma, g4.beta, [L['gnv'].v[t]], g4.mean[t], g4.rstd[t], groups=4, act='none')
+                    K.lnlstm_state_fwd(L['gnv'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), L['cpre'].v[t])
+                    K.groupnorm_act_fwd(L['cpre'].v[t], nS.gamma, nS.beta, [L['c'].v[t]], nS.mean[t], nS.rstd[t], groups=1, act='none')
+                    outs = self._out_views(L, t)
+                    if t + 1 < T1:
+                        outs.append(a.v[t + 1][..., f + L['zr']:f + L['zr'] + f])
+                    K.lnlstm_out_fwd(L['gnv'].v[t], L['c'].v[t], outs)
                 elif L['rnn']:
                     a = L['a']
                     self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, [a.v[t][..., 0:f]], t)
@@ -718,6 +804,12 @@ class SAVPGenerator(object):
                             self.masks[t] if collect_masks else None, M=self.M, next_inputs=nxt)
         return self.gen.v
 
+    def _norm(self, scope, c, kind=None, bias=None):
+        """The normalizer_fn of `kind` (default: norm_layer) under `scope`: <scope>InstanceNorm/ or <scope>LayerNorm/; bias: the variable
+        name of the bias of the convolution in front of it (a layer norm's backward can supply that bias's gradient)."""
+        kind = kind or self.hp.norm_layer
+        return Norm(self.store, scope + NORM_SCOPES[kind], self.T1, self.N, c, self.dev, groups=1 if kind == 'layer' else None, bias=bias)
+
     # ---------------------------------------------------------------------------------------------------------
     def _conv_norm(self, name, conv, x, pre, nrm, outs, t, **kw):
         """conv -> instance norm + ReLU of a head; the conv's epilogue supplies the norm's statistics where it can (see forward)."""
@@ -733,18 +825,20 @@ class SAVPGenerator(object):
         statistics slice the conv's epilogue fills for the norm (None: the norm takes its own)."""
         bias = getattr(conv, 'inner', conv).bias          # ConcatConv keeps the concatenated bias in its inner layer
         nkw = dict(act='relu', eps=EPS_IN, stats=st, stats_shift=bias if st is not None else None, **kw)
-        ca = conv.forward(x, pre, stats=st, defer=True) if (FUSED_ENTRIES and K.fused_ok()) else None
+        ca = conv.forward(x, pre, stats=st, defer=True) if (FUSED_ENTRIES and K.fused_ok() and nrm.groups is None) else None
         if ca is not None:
             K.conv_in_act_fwd(ca, K.instnorm_act_fwd(pre, nrm.gamma, nrm.beta, outs, nrm.mean[t], nrm.rstd[t], defer=True, **nkw))
         else:
             conv.forward(x, pre, stats=st)
-            K.instnorm_act_fwd(pre, nrm.gamma, nrm.beta, outs, nrm.mean[t], nrm.rstd[t], **nkw)
+            norm_fwd(nrm, pre, outs, nrm.mean[t], nrm.rstd[t], **nkw)
 
     def _norm_bwd(self, key, holder, conv, dy, dx, nrm, x, skip=None):
         """The instance norm (over x, parameters nrm) whose OUTPUT gradient is the channels [0, C) that conv.backward_data(dy, dx) is
         about to write: where the ring kernel can, its epilogue leaves that norm's backward sums behind (SavpConvArgs.nb_*), and the
         norm's backward is then ONE launch.  Returns the norm_bwd dict for backward_data (None: the norm takes its own sums); its 'ws'
         is what instnorm_act_bwd(stats=...) gets.  The decision is made once per layer (holder[key])."""
+        if nrm.groups is not None:            # the epilogue's sums take per-(sample, channel) statistics: the layer norm takes its own
+            return None
         t_ = dict(x=x, mean=nrm.mean[0], rstd=nrm.rstd[0], gamma=nrm.gamma, beta=nrm.beta, c0=0, act='relu')
         key = (key, K.PRECISION['value'])
         ok = holder.get(key)
@@ -764,11 +858,11 @@ class SAVPGenerator(object):
         (savp_conv_in_act_bwd).  st: the norm-backward sums a data gradient's epilogue has already left (None: the norm takes them)."""
         nrm = L['norm']
         nargs = (L['pre'].v[t], nrm.gamma, nrm.beta, y0, nrm.mean[t], nrm.rstd[t], dys, L['pre'].g[t], nrm.dgamma, nrm.dbeta)
-        if FUSED_ENTRIES and K.fused_ok():
+        if FUSED_ENTRIES and K.fused_ok() and nrm.groups is None:
             K.conv_in_act_bwd(L['conv'].backward_data(L['pre'].g[t], L['in'].g[t], beta=0, defer=True),
                               K.instnorm_act_bwd(*nargs, act='relu', eps=EPS_IN, stats=st, defer=True))
         else:
-            K.instnorm_act_bwd(*nargs, act='relu', eps=EPS_IN, stats=st)
+            norm_bwd(nrm, *nargs[:1], *nargs[3:], act='relu', eps=EPS_IN, stats=st)
             L['conv'].backward_data(L['pre'].g[t], L['in'].g[t], beta=0)
 
     def _lstm_ws(self, L):
@@ -838,7 +932,7 @@ class SAVPGenerator(object):
                 hn = self.heads_norm
                 dys = ([self.scratch_h.g[t]] if self.scratch else []) + [maskin.g[t][..., 0:ngf]] + \
                       ([self.tf_h.g[t]] if self.tf != 'cdna' else [])
-                K.instnorm_act_bwd(self.heads_pre.v[t], hn.gamma, hn.beta, None, hn.mean[t], hn.rstd[t], dys, self.heads_pre.g[t],
+                norm_bwd(hn, self.heads_pre.v[t], None, hn.mean[t], hn.rstd[t], dys, self.heads_pre.g[t],
                                    hn.dgamma, hn.dbeta, act='relu', eps=EPS_IN, dy_ranges=[(i * ngf, ngf) for i in range(self.nheads)])
                 Ll = self.layers[-1]
                 nb_last = None
@@ -851,17 +945,17 @@ class SAVPGenerator(object):
                 self.heads_conv.backward_data(self.heads_pre.g[t], self.h_last.g[t], beta=0, norm_bwd=nb_last)
             else:
                 mn = self.masks_norm
-                K.instnorm_act_bwd(self.masks_pre.v[t], mn.gamma, mn.beta, maskin.v[t][..., 0:ngf], mn.mean[t], mn.rstd[t],
+                norm_bwd(mn, self.masks_pre.v[t], maskin.v[t][..., 0:ngf], mn.mean[t], mn.rstd[t],
                                    [maskin.g[t][..., 0:ngf]], self.masks_pre.g[t], mn.dgamma, mn.dbeta, act='relu', eps=EPS_IN)
                 self.masks_conv.backward_data(self.masks_pre.g[t], self.h_last.g[t], beta=0)
                 if self.scratch:
                     sn = self.scratch_norm
-                    K.instnorm_act_bwd(self.scratch_pre.v[t], sn.gamma, sn.beta, self.scratch_h.v[t], sn.mean[t], sn.rstd[t],
+                    norm_bwd(sn, self.scratch_pre.v[t], self.scratch_h.v[t], sn.mean[t], sn.rstd[t],
                                        [self.scratch_h.g[t]], self.scratch_pre.g[t], sn.dgamma, sn.dbeta, act='relu', eps=EPS_IN)
                     self.scratch_conv.backward_data(self.scratch_pre.g[t], self.h_last.g[t], beta=1)
                 if self.tf != 'cdna':
                     tn = self.tf_norm
-                    K.instnorm_act_bwd(self.tf_pre.v[t], tn.gamma, tn.beta, self.tf_h.v[t], tn.mean[t], tn.rstd[t], [self.tf_h.g[t]],
+                    norm_bwd(tn, self.tf_pre.v[t], self.tf_h.v[t], tn.mean[t], tn.rstd[t], [self.tf_h.g[t]],
                                        self.tf_pre.g[t], tn.dgamma, tn.dbeta, act='relu', eps=EPS_IN)
                     self.tf_conv.backward_data(self.tf_pre.g[t], self.h_last.g[t], beta=1)
             if not self.merge_heads:
@@ -873,7 +967,7 @@ class SAVPGenerator(object):
                 nrm = L['norm']
                 if L['rnn'] and self.abl_rnn:
                     a, n2 = L['a'], L['n2']
-                    K.instnorm_act_bwd(L['pre2'].v[t], n2.gamma, n2.beta, self._out_views(L, t)[0], n2.mean[t], n2.rstd[t], dys, L['pre2'].g[t],
+                    norm_bwd(n2, L['pre2'].v[t], self._out_views(L, t)[0], n2.mean[t], n2.rstd[t], dys, L['pre2'].g[t],
                                        n2.dgamma, n2.dbeta, act='relu', eps=EPS_IN)
                     L['rconv'].backward_data(L['pre2'].g[t], a.g[t], beta=0)
                     self._in_act_conv_bwd(L, t, a.v[t][..., 0:f], [a.g[t][..., 0:f]], None)
@@ -893,13 +987,13 @@ class SAVPGenerator(object):
                                         a.g[t][..., rs_:rs_ + f], L['gates'].g[t], a.g[t][..., hs:hs + f], n1.dgamma, n1.dbeta,
                                         eps=EPS_IN)
                     L['rconv'].backward_data(L['gates'].g[t], a.g[t][..., 0:cin1], beta=1)
-                    K.instnorm_act_bwd(L['pre'].v[t], nrm.gamma, nrm.beta, a.v[t][..., 0:f], nrm.mean[t], nrm.rstd[t],
+                    norm_bwd(nrm, L['pre'].v[t], a.v[t][..., 0:f], nrm.mean[t], nrm.rstd[t],
                                        [a.g[t][..., 0:f]], L['pre'].g[t], nrm.dgamma, nrm.dbeta, act='relu', eps=EPS_IN)
                 elif L['rnn'] and self.cell_plain:
                     a = L['a']
                     if self.out_norm:
                         on = L['onorm']
-                        K.instnorm_act_bwd(L['h_raw'].v[t], on.gamma, on.beta, self._out_views(L, t)[0], on.mean[t], on.rstd[t], dys,
+                        norm_bwd(on, L['h_raw'].v[t], self._out_views(L, t)[0], on.mean[t], on.rstd[t], dys,
                                            L['h_raw'].g[t], on.dgamma, on.dbeta, act='none', eps=EPS_IN)
                         dys = [L['h_raw'].g[t]]
                     if t + 1 < T1:
@@ -915,9 +1009,21 @@ class SAVPGenerator(object):
                     a = L['a']
                     if t + 1 < T1:
                         dys.append(a.g[t + 1][..., f + L['zr']:f + L['zr'] + f])
-                    n1, n2 = L['n1'], L['n2']
                     dc_new = L['dc'][(t + 1) & 1] if t + 1 < T1 else None
                     dc_prev = L['dc'][t & 1] if (t > 0 or self.learn_init) else None
+                    if self.cell_ln:
+                        g4, nS, gnv, cpre = L['gn4'], L['nS'], L['gnv'], L['cpre']
+                        c_prev = L['c'].v[t - 1] if t > 0 else L.get('c0')
+                        K.lnlstm_out_bwd(gnv.v[t], L['c'].v[t], dys, dc_new, L['dcn'], gnv.g[t])
+                        K.groupnorm_act_bwd(cpre.v[t], nS.gamma, nS.beta, nS.mean[t], nS.rstd[t], [L['dcn']], cpre.g[t], nS.dgamma, nS.dbeta,
+                                            groups=1, act='none')
+                        K.lnlstm_state_bwd(gnv.v[t], c_prev, cpre.g[t], gnv.g[t], dc_prev)
+                        K.groupnorm_act_bwd(L['gates'].v[t], g4.gamma, g4.beta, g4.mean[t], g4.rstd[t], [gnv.g[t]], L['gates'].g[t],
+                                            g4.dgamma, g4.dbeta, groups=4, act='none')
+                        L['rconv'].backward_data(L['gates'].g[t], a.g[t], beta=0)
+                        self._in_act_conv_bwd(L, t, a.v[t][..., 0:f], [a.g[t][..., 0:f]], None)
+                        continue
+                    n1, n2 = L['n1'], L['n2']
                     bargs = (L['gates'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), n1.gamma, n1.beta, n2.gamma, n2.beta,
                              [n1.mean[t], n1.rstd[t], n2.mean[t], n2.rstd[t]], dys, dc_new, L['gates'].g[t], dc_prev,
                              [n1.dgamma, n1.dbeta, n2.dgamma, n2.dbeta])
@@ -964,6 +1070,8 @@ class SAVPGenerator(object):
             elif L['rnn']:
                 a, gt = L['a'], L['gates']
                 L['rconv'].backward_weights(a.flat(a.v), gt.flat(gt.g))
+                if 'gn4' in L:
+                    L['gn4'].finish()
         hl = self.h_last
         if self.tf == 'cdna':
             hs = self.hsmall

@@ -20,6 +20,9 @@ VIDEO_D_LAYERS = [  # (scope, ndf multiplier, kernel, strides(d,h,w))   networks
     ('sn_conv2_1', 8, 4, (2, 2, 2)),
     ('sn_conv3_0', 8, 3, (1, 1, 1)),
 ]
+# default variable scope of each normalizer_fn (ops.get_norm_layer, ops.py:1062-1074): fused_instance_norm -> 'InstanceNorm'
+# (layers/normalization.py:94), tf.contrib.layers.layer_norm -> 'LayerNorm'; 'none' is tf.identity (no variables)
+NORM_SCOPES = {'instance': 'InstanceNorm/', 'layer': 'LayerNorm/'}
 IMAGE_D_LAYERS = [  # networks.py:45-64
     ('sn_conv0_0', 1, 3, 1), ('sn_conv0_1', 2, 4, 2), ('sn_conv1_0', 2, 3, 1), ('sn_conv1_1', 4, 4, 2),
     ('sn_conv2_0', 4, 3, 1), ('sn_conv2_1', 8, 4, 2), ('sn_conv3_0', 8, 3, 1),
@@ -102,9 +105,9 @@ def generator_variable_specs(hp, image_shape, cond=(0, 0)):
             s = p + 'layer_%d/' % (i + 1)
             specs[s + 'conv2d/kernel'] = ((4, 4, cin, cout), 'tn0.02')
             specs[s + 'conv2d/bias'] = ((cout,), 'zeros')
-            if i > 0 and hp.norm_layer == 'instance':
-                specs[s + 'InstanceNorm/beta'] = ((cout,), 'zeros')
-                specs[s + 'InstanceNorm/gamma'] = ((cout,), 'ones')
+            if i > 0 and hp.norm_layer in NORM_SCOPES:
+                specs[s + NORM_SCOPES[hp.norm_layer] + 'beta'] = ((cout,), 'zeros')
+                specs[s + NORM_SCOPES[hp.norm_layer] + 'gamma'] = ((cout,), 'ones')
             cin = cout
         if recurrent:
             u = hp.nef * 4
@@ -133,10 +136,10 @@ def generator_variable_specs(hp, image_shape, cond=(0, 0)):
     zc = zw if tile else 0          # channels added by tile_concat
     enc, dec = layer_specs(hp.ngf, H, W)
 
-    def norm(scope, c):
-        if hp.norm_layer == 'instance':
-            specs[scope + 'InstanceNorm/beta'] = ((c,), 'zeros')
-            specs[scope + 'InstanceNorm/gamma'] = ((c,), 'ones')
+    def norm(scope, c, kind=hp.norm_layer):
+        if kind in NORM_SCOPES:
+            specs[scope + NORM_SCOPES[kind] + 'beta'] = ((c,), 'zeros')
+            specs[scope + NORM_SCOPES[kind] + 'gamma'] = ((c,), 'ones')
 
     ablation_rnn = bool(getattr(hp, 'ablation_rnn', False))
     cell_norm = hp.conv_rnn_norm_layer != 'none' and not getattr(hp, 'ablation_conv_rnn_norm', False)
@@ -153,8 +156,7 @@ def generator_variable_specs(hp, image_shape, cond=(0, 0)):
             return
         if getattr(hp, 'ablation_conv_rnn_norm', False) and hp.conv_rnn_norm_layer != 'none':
             # :380-384: the cell is built without a normalizer; normalizer_fn(h) keeps its variables in its default scope beside the cell's
-            specs[scope + 'InstanceNorm/beta'] = ((f,), 'zeros')
-            specs[scope + 'InstanceNorm/gamma'] = ((f,), 'ones')
+            norm(scope, f, hp.conv_rnn_norm_layer)
         if hp.conv_rnn == 'lstm':
             s = scope + 'basic_conv2dlstm_cell/'
             specs[s + 'kernel'] = ((5, 5, cin + f, 4 * f), 'tn0.02')
@@ -162,6 +164,11 @@ def generator_variable_specs(hp, image_shape, cond=(0, 0)):
                 specs[s + 'weights'] = ((zw, 4 * f), 'tn0.02')
             if not cell_norm:
                 specs[s + 'bias'] = ((4 * f,), 'zeros')
+            elif hp.conv_rnn_norm_layer == 'layer':
+                # separate_norms (rnn_ops.py:102-112,151-164): each gate and the new state normalised on their own, <cell>/<name>/{gamma,beta}
+                for name in ('input', 'transform', 'forget', 'output', 'state'):
+                    specs[s + name + '/gamma'] = ((f,), 'ones')
+                    specs[s + name + '/beta'] = ((f,), 'zeros')
             else:
                 specs[s + 'input_transform_forget_output/gamma'] = ((4 * f,), 'ones')
                 specs[s + 'input_transform_forget_output/beta'] = ((4 * f,), 'zeros')
