@@ -139,7 +139,8 @@ typedef struct SavpConvArgs {
     const float *nb_mean, *nb_rstd;                  /* [N][nb_nc] saved by the forward pass */
     const float *nb_gamma, *nb_beta;                 /* [nb_nc] */
     double* nb_ws;                                   /* [N][nb_nc][2] FLOAT64 (see `stats`) */
-    int32_t nb_c0, nb_nc, nb_act; float nb_alpha;    /* nb_act: 0 none, 1 relu, 2 leaky relu (nb_alpha) */
+    int32_t nb_c0, nb_nc, nb_act; float nb_alpha;    /* nb_act: 0 none, 1 relu, 2 leaky relu (nb_alpha); 3 (elu) is SAVP_EINVAL here: an ELU
+                                                        norm takes its own backward sums */
     /* Round 6, the ConvLSTM gate convolution's own kernel (conv_gate.hip; rnn_ops.py:115-126,143): the weights once more, in MFMA B-fragment
        order (savp_pack_gate_weights; savp_gate_weights_bytes of them, 16-byte aligned).  Given it, a 2-D 5x5 stride-1 SAME FPROP between dense
        bf16 tensors with `stats` (bias / act / beta / aux none, Cy % 128 == 0, H == W and (H, Cx) one of the instantiated shapes) takes that
@@ -187,13 +188,15 @@ int savp_conv_special(const SavpConvArgs* args);
 typedef struct SavpView { void* p; int64_t sn; int64_t sp; } SavpView;
 
 /* ------------------------------------------------------------------------------------------------------------
- * fused_instance_norm (+ ReLU / LeakyReLU), eps 1e-6, biased variance  (layers/normalization.py:146-170;
+ * fused_instance_norm (+ ReLU / LeakyReLU / ELU), eps 1e-6, biased variance  (layers/normalization.py:146-170;
  * call sites savp_model.py:463-464,499-500,564-565,627-628; networks.py:26-27).
  * fwd: out[k] = act(gamma*(x-mean)/sqrt(var+eps)+beta) for k < nout (multi-destination so that concat buffers are
  *      filled without copy kernels); saves mean/rstd [N,C].
  * bwd: dy = sum_k dy[k]; masks by the saved activation output out[0]; writes dx (accumulates if dx_beta) and
- *      atomically accumulates dgamma/dbeta.   act: 0 none, 1 relu, 2 lrelu(alpha).  The activation mask is recomputed from
- *      x, mean, rstd, gamma, beta (y > 0 <=> z > 0): bwd does not read the saved output (`out` is ignored).
+ *      atomically accumulates dgamma/dbeta.   act: 0 none, 1 relu, 2 lrelu(alpha), 3 elu (tf.nn.elu: z > 0 ? z : exp(z) - 1, the
+ *      generator's activation_layer = 'elu').  The activation's derivative is recomputed from the pre-activation z, itself recomputed
+ *      from x, mean, rstd, gamma, beta (a 0 / 1 / alpha mask for 1 and 2, z > 0 ? 1 : exp(z) for 3): bwd does not read the saved output
+ *      (`out` is ignored).
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct SavpInormArgs {
     int32_t N, HW, C;
@@ -230,7 +233,7 @@ int savp_instnorm_act_fwd(void* stream, const SavpInormArgs* a);
 int savp_instnorm_act_bwd(void* stream, const SavpInormArgs* a);
 
 /* ------------------------------------------------------------------------------------------------------------
- * Normalisation (+ ReLU / LeakyReLU) with statistics shared by G groups of C/G consecutive channels (group_norm.hip).
+ * Normalisation (+ ReLU / LeakyReLU / ELU, the codes of SavpInormArgs.act) with statistics shared by G groups of C/G consecutive channels (group_norm.hip).
  * G = 1 is tf.contrib.layers.layer_norm with its defaults (begin_norm_axis = 1, begin_params_axis = -1: mean and biased variance
  * per sample over H, W and C, gamma / beta [C], eps 1e-12), the reference's norm_layer = 'layer' (ops.py:1062-1074; call sites
  * savp_model.py:463-464,477,499-500,512,525,537,564,627, networks.py:26-27); G = C is the instance norm above.
@@ -516,6 +519,10 @@ typedef struct {
 } SavpPackItem;
 int savp_pack_weights_batch(void* stream, int32_t n, const SavpPackItem* items);
 int savp_fold_pool(void* stream, const float* in, float* out, int32_t k, int64_t C, int32_t adjoint);
+/* in [k][k][C] -> out [k+1][k+1][C], out[a][b] = in[a-1][b-1], zero where a == 0 or b == 0: a k x k stride-2 SAME kernel (ops.conv2d
+ * :494-550 with strides 2; the forward description of ops.deconv2d :553-589) in the (k+1)-tap stride-2 geometry of the folded conv_pool2d
+ * kernel.  adjoint: out [k][k][C] += in[1..][1..]. */
+int savp_fold_embed(void* stream, const float* in, float* out, int32_t k, int64_t C, int32_t adjoint);
 int savp_fold_bilinear(void* stream, const float* in, float* out, int32_t k, int32_t Cin, int32_t F, int32_t adjoint);
 /* ws: 8 + 2C + 2K + 2 (C + 2) floats, 8-byte aligned (the tail holds float64 accumulators of the forward sums: exact, order-independent); after fwd ws[0]=sigma, ws[1]=1/sigma; u_new receives u_final */
 int savp_sn_fwd(void* stream, const float* W, int64_t K, int32_t C, const float* u, float* ws, float* u_new);

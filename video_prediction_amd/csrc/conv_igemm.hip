@@ -860,6 +860,7 @@ extern "C" int savp_conv_stats_ok(const SavpConvArgs* a) {
     p.gap_at = a->dst_gap ? a->dst_gap_at : 0x7fffffff; p.gap = a->dst_gap;
     p.nb_ws = (double*)a->nb_ws; p.nb_c0 = a->nb_c0; p.nb_nc = a->nb_nc; p.part = nullptr; p.part_sz = 0;
     if (a->dst_gap && !a->nb_ws) return 0;                      // forward statistics of a gapped destination: not offered
+    if (a->nb_ws && (a->nb_act < 0 || a->nb_act > 2)) return 0;   // the epilogue knows the 0 / 1 / alpha masks (savp_conv: SAVP_EINVAL); an ELU norm takes its own sums
     SavpConvArgs b = *a;
     if (!b.stats && !b.nb_ws) b.stats = (double*)(uintptr_t)16;   // any non-NULL value: only the plan is made
     int wm = 0, wn = 0;

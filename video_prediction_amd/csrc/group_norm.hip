@@ -34,11 +34,13 @@ __device__ __forceinline__ void gn_st4x(float* base, long long idx, float4 v, in
 __device__ __forceinline__ float gn_act(float v, int act, float alpha) {
     if (act == 1) return fmaxf(v, 0.f);
     if (act == 2) return fmaxf(v, alpha * v);
+    if (act == 3) return v > 0.f ? v : expm1f(v);             // tf.nn.elu
     return v;
 }
 __device__ __forceinline__ float gn_act_grad(float z, int act, float alpha) {      // from the pre-activation: y > 0 <=> z > 0
     if (act == 1) return z > 0.f ? 1.f : 0.f;
     if (act == 2) return z > 0.f ? 1.f : alpha;
+    if (act == 3) return z > 0.f ? 1.f : expf(z);             // ELU: no mask, the factor exp(z) where z <= 0
     return 1.f;
 }
 

@@ -75,11 +75,15 @@ __device__ __forceinline__ void st4x(float* base, long long idx, float4 v, int i
 __device__ __forceinline__ float act_fwd(float v, int act, float alpha) {
     if (act == 1) return fmaxf(v, 0.f);
     if (act == 2) return fmaxf(v, alpha * v);
+    if (act == 3) return v > 0.f ? v : expm1f(v);             // tf.nn.elu
     return v;
 }
+// every caller hands in the recomputed pre-activation z = gamma * xhat + beta (y > 0 <=> z > 0 for the three masks); ELU needs z itself:
+// its derivative is exp(z) where z <= 0
 __device__ __forceinline__ float act_grad_from_out(float y, int act, float alpha) {
     if (act == 1) return y > 0.f ? 1.f : 0.f;
     if (act == 2) return y > 0.f ? 1.f : alpha;
+    if (act == 3) return y > 0.f ? 1.f : expf(y);
     return 1.f;
 }
 

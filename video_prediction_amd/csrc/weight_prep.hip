@@ -4,6 +4,8 @@
 //                      (1/sigma of spectral normalisation).
 //   fold_pool        : conv_pool2d's avg-pool folding of the kernel (ops.py:838-842) and its adjoint.
 //   fold_bilinear    : upsample_conv2d's bilinear folding (ops.py:697-704) and its adjoint.
+//   fold_embed       : a k x k stride-2 SAME kernel (ops.conv2d / ops.deconv2d) set into the (k+1) x (k+1) geometry of the folded
+//                      conv_pool2d kernel (taps at rows / columns 1..k, row and column 0 zero) and its adjoint.
 //   sn_*             : spectral_normed_weight (ops.py:1020-1049), one power iteration, forward and the full
 //                      backward (gradients flow through sigma, u', v -- the reference has no stop_gradient).
 #include <hip/hip_runtime.h>
@@ -169,6 +171,34 @@ extern "C" int savp_fold_pool(void* stream, const float* in, float* out, int32_t
     unsigned nb = (unsigned)((total + NT - 1) / NT);
     if (nb > 8192) nb = 8192;
     hipLaunchKernelGGL(fold_pool_kernel, dim3(nb), dim3(NT), 0, (hipStream_t)stream, in, out, k, (long long)C, adjoint);
+    return LAUNCH_OK();
+}
+
+// fold_embed: src [k,k,C] -> dst [k+1,k+1,C], dst[a][b] = src[a-1][b-1] (zero where a == 0 or b == 0).  On an even plane the stride-2 SAME
+// convolution pads k - 2 in total, the smaller half first ((k-2)/2 before); the (k+1)-tap geometry pads (k-1)/2 before, one more, so the
+// k x k taps sit one row and one column in.  adjoint: dsrc[k,k,C] += ddst[1.., 1..] (the gradient of the zero row / column is dropped).
+__global__ void fold_embed_kernel(const float* __restrict__ in, float* __restrict__ out, int k, long long C, int adjoint) {
+    const int ko = k + 1;
+    const long long total = adjoint ? (long long)k * k * C : (long long)ko * ko * C;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long c = i % C;
+        const long long r = i / C;
+        if (!adjoint) {
+            const int b = (int)(r % ko), a = (int)(r / ko);
+            out[i] = (a > 0 && b > 0) ? in[((long long)(a - 1) * k + (b - 1)) * C + c] : 0.f;
+        } else {
+            const int v = (int)(r % k), u = (int)(r / k);
+            out[i] += in[((long long)(u + 1) * ko + (v + 1)) * C + c];
+        }
+    }
+}
+
+extern "C" int savp_fold_embed(void* stream, const float* in, float* out, int32_t k, int64_t C, int32_t adjoint) {
+    if (!in || !out || k < 1 || C < 1) return SAVP_EINVAL;
+    long long total = (long long)(k + 1) * (k + 1) * C;
+    unsigned nb = (unsigned)((total + NT - 1) / NT);
+    if (nb > 8192) nb = 8192;
+    hipLaunchKernelGGL(fold_embed_kernel, dim3(nb), dim3(NT), 0, (hipStream_t)stream, in, out, k, (long long)C, adjoint);
     return LAUNCH_OK();
 }
 

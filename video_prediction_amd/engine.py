@@ -205,6 +205,9 @@ def same_pad_before(k, s, in_size):
     return total // 2
 
 
+TRANSPOSED = ('up', 'deconv')       # kinds executed as the DGRAD mode of the forward convolution their geometry describes
+
+
 class ConvLayer(object):
     """One convolution of the SAVP graph with its derived weight layouts.
 
@@ -213,6 +216,12 @@ class ConvLayer(object):
       'pool' : ops.conv_pool2d -- avg-pool folded into the kernel (k -> k+1), stride 2, SAME.
       'up'   : ops.upsample_conv2d -- bilinear x2 folded into the kernel (3 -> 6), conv2d_transpose stride 2 SAME;
                executed as the DGRAD mode of the stride-2 forward conv described by ``geom``.
+      'down' : ops.conv2d with strides (2, 2), SAME (downsample_layer = 'conv2d') -- the k x k kernel embedded in the (k+1) x (k+1)
+               stride-2 geometry of 'pool' (taps at rows / columns 1..k, row / column 0 zero: SAME pads (k-2)/2 before on an even plane,
+               the (k+1)-tap geometry one more), so it runs the instantiations tuned for 'pool'.
+      'deconv': ops.deconv2d -- tf.nn.conv2d_transpose, stride 2, SAME, kernel [k, k, F, Cin] (output channels first): by definition the
+               data gradient of the 'down' convolution F -> Cin with that very kernel, so it runs as the DGRAD mode like 'up', the
+               kernel embedded as for 'down' (no bilinear fold, no channel transposition).
     ``sn_u`` names the spectral-norm vector of a discriminator layer (kernel is divided by sigma on the fly).
     """
 
@@ -243,6 +252,13 @@ class ConvLayer(object):
             self.wf = torch.empty(k + 3, k + 3, f, cin, device=dev)
             self.dwf = torch.zeros_like(self.wf)
             k3 = (1, k + 3, k + 3)
+        elif kind in ('down', 'deconv'):
+            # 'down': [k, k, Cin, Cout]; 'deconv': [k, k, F, Cin] = the forward description's (x-side hi-res F, y-side lo-res Cin) as stored
+            k, _, cx, cy = W.shape
+            self.cx, self.cy = cx, cy
+            self.wf = torch.empty(k + 1, k + 1, cx, cy, device=dev)
+            self.dwf = torch.zeros_like(self.wf)
+            k3 = (1, k + 1, k + 1)
         else:
             raise ValueError(kind)
         if len(k3) == 2:
@@ -256,7 +272,7 @@ class ConvLayer(object):
         self.cx0, self.cy0 = self.cx, self.cy
         self.padded = False
         if (cx_pad and cx_pad != self.cx) or (cy_pad and cy_pad != self.cy):
-            if kind == 'up' or sn_u:
+            if kind in ('up', 'deconv') or sn_u:
                 raise NotImplementedError('channel padding for upsample / spectral-norm layers')
             self.padded = True
             self.cx, self.cy = cx_pad or self.cx, cy_pad or self.cy
@@ -301,6 +317,8 @@ class ConvLayer(object):
         elif self.kind == 'up':
             k, _, cin, f = self.W.shape
             K.fold_bilinear(self.W, self.wf, k, cin, f)
+        elif self.kind in ('down', 'deconv'):
+            K.fold_embed(self.W, self.wf, self.W.shape[0])
         if self.sn_u_name:
             if not sn_done:
                 K.sn_fwd(self.W, self.u.reshape(-1), self.sn_ws, self.u_next.reshape(-1) if update_u else None)
@@ -353,7 +371,7 @@ class ConvLayer(object):
         if defer:
             if self.ktimer is not None or self.prof is not None:
                 return None
-            if self.kind == 'up':
+            if self.kind in TRANSPOSED:
                 return K.conv(lib.CONV_DGRAD, self.geom, y, x, self.wd, bias=b, beta=beta, act=act, alpha=alpha, w16=self.wd16, stats=stats,
                               defer=True)
             return K.conv(lib.CONV_FPROP, self.geom, x, y, self.wt, bias=b, beta=beta, act=act, alpha=alpha, w16=self.wt16, stats=stats,
@@ -363,7 +381,7 @@ class ConvLayer(object):
         if self.prof is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        if self.kind == 'up':
+        if self.kind in TRANSPOSED:
             K.conv(lib.CONV_DGRAD, self.geom, y, x, self.wd, bias=b, beta=beta, act=act, alpha=alpha, w16=self.wd16, stats=stats)
         else:
             K.conv(lib.CONV_FPROP, self.geom, x, y, self.wt, bias=b, beta=beta, act=act, alpha=alpha, w16=self.wt16, stats=stats, w_frag=self.wfrag)
@@ -377,7 +395,7 @@ class ConvLayer(object):
         """Can forward(x, y, stats=...) leave the destination's instance-norm statistics behind (kernels.conv_stats_ok)?"""
         if K.PRECISION['value'] != 1:
             return False
-        if self.kind == 'up':
+        if self.kind in TRANSPOSED:
             return K.conv_stats_ok(lib.CONV_DGRAD, self.geom, y, x, self.wd, bias=self.bias, w16=self.wd16)
         return K.conv_stats_ok(lib.CONV_FPROP, self.geom, x, y, self.wt, bias=self.bias, w16=self.wt16)
 
@@ -385,7 +403,7 @@ class ConvLayer(object):
         """skip = (first, count): input channels whose data gradient is not needed per pixel (left unwritten in dx).  norm_bwd: dx's
         channels [c0, c0 + C) are the output gradient of an instance norm over norm_bwd['x']; its backward sums leave with this launch
         (kernels.conv)."""
-        if self.kind == 'up':
+        if self.kind in TRANSPOSED:
             return K.conv(lib.CONV_FPROP, self.geom, dy, dx, self.wt, beta=beta, act=act, alpha=alpha, aux=aux, w16=self.wt16, dst_gap=skip,
                           norm_bwd=norm_bwd, defer=defer)
         return K.conv(lib.CONV_DGRAD, self.geom, dx, dy, self.wd, beta=beta, act=act, alpha=alpha, aux=aux, w16=self.wd16, dst_gap=skip,
@@ -396,7 +414,7 @@ class ConvLayer(object):
         if K.PRECISION['value'] != 1:
             return False
         nb = dict(norm_bwd, ws=None)
-        if self.kind == 'up':
+        if self.kind in TRANSPOSED:
             return K.conv_stats_ok(lib.CONV_FPROP, self.geom, dy, dx, self.wt, w16=self.wt16, dst_gap=skip, norm_bwd=nb)
         return K.conv_stats_ok(lib.CONV_DGRAD, self.geom, dx, dy, self.wd, w16=self.wd16, dst_gap=skip, norm_bwd=nb)
 
@@ -415,7 +433,7 @@ class ConvLayer(object):
         # sums of the bf16-ROUNDED gradient would be noise 2^-9 / 2^-24 times larger (measured 2e-3 of the group's largest gradient at
         # T = 40), so with a bf16 dy the bias gradient is left at its exact value, zero.
         db = None if (feeds_instance_norm and dy.dtype == torch.bfloat16) else self.dbias
-        if self.kind == 'up':
+        if self.kind in TRANSPOSED:
             K.conv(lib.CONV_WGRAD, self.geom, dy, x, target)
             if db is not None:
                 K.colsum(dy, db)
@@ -442,6 +460,8 @@ class ConvLayer(object):
         elif self.kind == 'up':
             k, _, cin, f = self.W.shape
             K.fold_bilinear(self.dwf, self.dW, k, cin, f, adjoint=True)
+        elif self.kind in ('down', 'deconv'):
+            K.fold_embed(self.dwf, self.dW, self.W.shape[0], adjoint=True)
         self.dwf.zero_()
 
 

@@ -393,7 +393,7 @@ def conv_stats_ok(mode, geom, x, y, w, bias=None, w16=None, dst_gap=None, norm_b
     return bool(lib.get().savp_conv_stats_ok(ctypes.byref(a)))
 
 
-ACT_IDS = {None: 0, 'none': 0, 'relu': 1, 'lrelu': 2}
+ACT_IDS = {None: 0, 'none': 0, 'relu': 1, 'lrelu': 2, 'elu': 3}      # 'elu': the norm entries only (SavpConvArgs.nb_act stops at 2)
 
 
 def view(t, any_dtype=False):
@@ -1346,6 +1346,15 @@ def pack_gate_weights(src, out, interleave=False):
 def fold_pool(inp, out, k, adjoint=False):
     C = (out.numel() if adjoint else inp.numel()) // (k * k)
     lib.check(_L().savp_fold_pool(lib.stream(), _p(inp), _p(out), k, C, int(adjoint)), 'savp_fold_pool')
+
+
+def fold_embed(inp, out, k, adjoint=False):
+    """[k, k, ...] -> [k+1, k+1, ...] with the taps at rows / columns 1..k and a zero row / column 0 (the stride-2 SAME convolution in
+    the folded conv_pool2d geometry); adjoint: out [k, k, ...] += inp[1:, 1:]."""
+    C = (out.numel() if adjoint else inp.numel()) // (k * k)
+    if (inp.numel() if adjoint else out.numel()) != (k + 1) * (k + 1) * C:
+        raise ValueError('fold_embed: %s <-> %s with k = %d' % (tuple(inp.shape), tuple(out.shape), k))
+    lib.check(_L().savp_fold_embed(lib.stream(), _p(inp), _p(out), k, C, int(adjoint)), 'savp_fold_embed')
 
 
 def fold_bilinear(inp, out, k, Cin, F, adjoint=False):

@@ -360,6 +360,7 @@ register('savp_lsgan_loss', [c_vp, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_i32]
 register('savp_cosine_distance', [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_f32, c_vp, c_vp, c_i32])
 register('savp_pack_weights', [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp])
 register('savp_fold_pool', [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32])
+register('savp_fold_embed', [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32])
 register('savp_fold_bilinear', [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])
 class SavpPackItem(ctypes.Structure):
     _fields_ = [('src', c_vp), ('scale', c_vp), ('wt', c_vp), ('wd', c_vp), ('wt_bf16', c_vp), ('wd_bf16', c_vp), ('T', c_i64),

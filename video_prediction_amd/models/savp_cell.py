@@ -20,7 +20,7 @@ import torch
 from .. import kernels as K
 from .. import lib
 from ..engine import ConcatConv, ConvLayer, same_pad_before, copy_view, add_views, prep_layers
-from ..variables import NORM_SCOPES, layer_specs, num_masks
+from ..variables import ACTIVATIONS, NORM_SCOPES, down_scope, layer_specs, num_masks, up_scope
 
 CONV_STATS = os.environ.get('SAVP_CONV_STATS', '1') == '1'      # developer A/B switch of the conv-epilogue statistics
 FUSED_ENTRIES = os.environ.get('SAVP_FUSED_ENTRIES', '1') == '1'      # one host call per fused operator (csrc/fused_ops.hip); 0: the halves apart
@@ -185,8 +185,13 @@ class SAVPGenerator(object):
             raise TypeError("ablation_conv_rnn_norm with conv_rnn_norm_layer='none': the reference calls normalizer_fn = None (savp_model.py:384)")
         if self.cell_plain and hp.conv_rnn != 'lstm' and not hp.ablation_rnn:
             raise NotImplementedError('the normaliser-free cell is on the HIP path for conv_rnn = lstm only')
-        if hp.downsample_layer != 'conv_pool2d' or hp.upsample_layer != 'upsample_conv2d' or hp.activation_layer != 'relu':
-            raise NotImplementedError('HIP path covers conv_pool2d / upsample_conv2d / relu')
+        # downsample_layer / upsample_layer / activation_layer (ops.py:1052-1098; savp_model.py:395-397).  conv2d: the strided SAME
+        # convolution, ConvLayer kind 'down'; deconv2d: conv2d_transpose, kind 'deconv'; the _v2 names are aliases (variables.DOWN_SCOPES).
+        # elu: the activation code of every norm_layer site of the cell (the ladder, ablation_rnn's conv_h<i>, the 3x3 heads).
+        self.down_op, self.up_op = down_scope(hp), up_scope(hp)
+        if hp.activation_layer not in ACTIVATIONS:
+            raise ValueError('Invalid activation layer %s' % hp.activation_layer)
+        self.act = hp.activation_layer
         if hp.transformation not in ('cdna', 'flow', 'dna') or hp.last_frames < 1 or not hp.num_transformed_images:
             raise NotImplementedError('HIP path covers transformation in (cdna, flow, dna) with last_frames >= 1 and num_transformed_images >= 1')
         # the multi-source transformation kernels (csrc/cdna_composite.hip, csrc/warp_dna.hip) take up to lib.MAX_SOURCES source frames
@@ -262,7 +267,9 @@ class SAVPGenerator(object):
                 L['in'] = Act((T1, N, h_, w_, ceil8(cx + zc)), dev, grad=g,      # pad channels stay zero
                               dtype=a16 if i > 0 else torch.float32)     # layer 0 holds the input image: fp32
                 L['zoff_in'] = cx
-                L['conv'] = ConvLayer(store, s + 'conv_pool2d/kernel', s + 'conv_pool2d/bias', 'pool', (k, k), (2, 2),
+                # 'down' (ops.conv2d, strides 2, SAME) runs in the folded pool kernel's (k+1)-tap geometry: engine.ConvLayer
+                L['conv'] = ConvLayer(store, s + self.down_op + '/kernel', s + self.down_op + '/bias',
+                                      'pool' if self.down_op == 'conv_pool2d' else 'down', (k, k), (2, 2),
                                       (same_pad_before(k + 1, 2, h_), same_pad_before(k + 1, 2, w_)),
                                       cx_pad=ceil8(cx + zc))
                 h_, w_ = h_ // 2, w_ // 2
@@ -274,8 +281,12 @@ class SAVPGenerator(object):
                 L['zoff_in'] = cx
                 L['skip_off'] = prev_f
                 h_, w_ = h_ * 2, w_ * 2
-                L['conv'] = ConvLayer(store, s + 'upsample_conv2d/kernel', s + 'upsample_conv2d/bias', 'up', (3, 3), (2, 2),
-                                      (same_pad_before(6, 2, h_), same_pad_before(6, 2, w_)))
+                if self.up_op == 'deconv2d':          # the data gradient of the 3x3 'down' convolution: its 4-tap geometry
+                    L['conv'] = ConvLayer(store, s + 'deconv2d/kernel', s + 'deconv2d/bias', 'deconv', (3, 3), (2, 2),
+                                          (same_pad_before(4, 2, h_), same_pad_before(4, 2, w_)))
+                else:
+                    L['conv'] = ConvLayer(store, s + 'upsample_conv2d/kernel', s + 'upsample_conv2d/bias', 'up', (3, 3), (2, 2),
+                                          (same_pad_before(6, 2, h_), same_pad_before(6, 2, w_)))
             L['hw'] = (h_, w_)
             # (a decoder layer whose input keeps an odd channel count -- conditioning widths that are no multiple of 8 -- stays fp32 on both
             #  sides: the weight gradient of an upsample conv reads the input as its `dy` operand, and only whole 4-channel groups ride
@@ -684,7 +695,7 @@ class SAVPGenerator(object):
                     a = L['a']
                     hs, rs_, cin1 = f + L['zr'], f + L['zr'] + f, L['cin1']
                     norm_fwd(nrm, L['pre'].v[t], [a.v[t][..., 0:f]], nrm.mean[t], nrm.rstd[t],
-                             act='relu', eps=EPS_IN, stats=st, stats_shift=L['conv'].bias if st is not None else None)
+                             act=self.act, eps=EPS_IN, stats=st, stats_shift=L['conv'].bias if st is not None else None)
                     n1, n2 = L['n1'], L['n2']
                     hprev = a.v[t][..., hs:hs + f]
                     L['rconv'].forward(a.v[t][..., 0:cin1], L['gates'].v[t], use_bias=False)
@@ -824,7 +835,7 @@ class SAVPGenerator(object):
         """conv -> fused_instance_norm + ReLU as ONE host call (savp_conv_in_act_fwd) where nothing instruments the conv; st = the
         statistics slice the conv's epilogue fills for the norm (None: the norm takes its own)."""
         bias = getattr(conv, 'inner', conv).bias          # ConcatConv keeps the concatenated bias in its inner layer
-        nkw = dict(act='relu', eps=EPS_IN, stats=st, stats_shift=bias if st is not None else None, **kw)
+        nkw = dict(act=self.act, eps=EPS_IN, stats=st, stats_shift=bias if st is not None else None, **kw)
         ca = conv.forward(x, pre, stats=st, defer=True) if (FUSED_ENTRIES and K.fused_ok() and nrm.groups is None) else None
         if ca is not None:
             K.conv_in_act_fwd(ca, K.instnorm_act_fwd(pre, nrm.gamma, nrm.beta, outs, nrm.mean[t], nrm.rstd[t], defer=True, **nkw))
@@ -839,7 +850,9 @@ class SAVPGenerator(object):
         is what instnorm_act_bwd(stats=...) gets.  The decision is made once per layer (holder[key])."""
         if nrm.groups is not None:            # the epilogue's sums take per-(sample, channel) statistics: the layer norm takes its own
             return None
-        t_ = dict(x=x, mean=nrm.mean[0], rstd=nrm.rstd[0], gamma=nrm.gamma, beta=nrm.beta, c0=0, act='relu')
+        if self.act == 'elu':                 # the epilogue knows the 0 / 1 / alpha masks only (SavpConvArgs.nb_act): an ELU norm takes its own
+            return None
+        t_ = dict(x=x, mean=nrm.mean[0], rstd=nrm.rstd[0], gamma=nrm.gamma, beta=nrm.beta, c0=0, act=self.act)
         key = (key, K.PRECISION['value'])
         ok = holder.get(key)
         if ok is None:
@@ -860,9 +873,9 @@ class SAVPGenerator(object):
         nargs = (L['pre'].v[t], nrm.gamma, nrm.beta, y0, nrm.mean[t], nrm.rstd[t], dys, L['pre'].g[t], nrm.dgamma, nrm.dbeta)
         if FUSED_ENTRIES and K.fused_ok() and nrm.groups is None:
             K.conv_in_act_bwd(L['conv'].backward_data(L['pre'].g[t], L['in'].g[t], beta=0, defer=True),
-                              K.instnorm_act_bwd(*nargs, act='relu', eps=EPS_IN, stats=st, defer=True))
+                              K.instnorm_act_bwd(*nargs, act=self.act, eps=EPS_IN, stats=st, defer=True))
         else:
-            norm_bwd(nrm, *nargs[:1], *nargs[3:], act='relu', eps=EPS_IN, stats=st)
+            norm_bwd(nrm, *nargs[:1], *nargs[3:], act=self.act, eps=EPS_IN, stats=st)
             L['conv'].backward_data(L['pre'].g[t], L['in'].g[t], beta=0)
 
     def _lstm_ws(self, L):
@@ -933,7 +946,7 @@ class SAVPGenerator(object):
                 dys = ([self.scratch_h.g[t]] if self.scratch else []) + [maskin.g[t][..., 0:ngf]] + \
                       ([self.tf_h.g[t]] if self.tf != 'cdna' else [])
                 norm_bwd(hn, self.heads_pre.v[t], None, hn.mean[t], hn.rstd[t], dys, self.heads_pre.g[t],
-                                   hn.dgamma, hn.dbeta, act='relu', eps=EPS_IN, dy_ranges=[(i * ngf, ngf) for i in range(self.nheads)])
+                                   hn.dgamma, hn.dbeta, act=self.act, eps=EPS_IN, dy_ranges=[(i * ngf, ngf) for i in range(self.nheads)])
                 Ll = self.layers[-1]
                 nb_last = None
                 if not Ll['rnn']:          # h_last is the output of the last layer's instance norm: its backward sums leave with this DGRAD
@@ -946,17 +959,17 @@ class SAVPGenerator(object):
             else:
                 mn = self.masks_norm
                 norm_bwd(mn, self.masks_pre.v[t], maskin.v[t][..., 0:ngf], mn.mean[t], mn.rstd[t],
-                                   [maskin.g[t][..., 0:ngf]], self.masks_pre.g[t], mn.dgamma, mn.dbeta, act='relu', eps=EPS_IN)
+                                   [maskin.g[t][..., 0:ngf]], self.masks_pre.g[t], mn.dgamma, mn.dbeta, act=self.act, eps=EPS_IN)
                 self.masks_conv.backward_data(self.masks_pre.g[t], self.h_last.g[t], beta=0)
                 if self.scratch:
                     sn = self.scratch_norm
                     norm_bwd(sn, self.scratch_pre.v[t], self.scratch_h.v[t], sn.mean[t], sn.rstd[t],
-                                       [self.scratch_h.g[t]], self.scratch_pre.g[t], sn.dgamma, sn.dbeta, act='relu', eps=EPS_IN)
+                                       [self.scratch_h.g[t]], self.scratch_pre.g[t], sn.dgamma, sn.dbeta, act=self.act, eps=EPS_IN)
                     self.scratch_conv.backward_data(self.scratch_pre.g[t], self.h_last.g[t], beta=1)
                 if self.tf != 'cdna':
                     tn = self.tf_norm
                     norm_bwd(tn, self.tf_pre.v[t], self.tf_h.v[t], tn.mean[t], tn.rstd[t], [self.tf_h.g[t]],
-                                       self.tf_pre.g[t], tn.dgamma, tn.dbeta, act='relu', eps=EPS_IN)
+                                       self.tf_pre.g[t], tn.dgamma, tn.dbeta, act=self.act, eps=EPS_IN)
                     self.tf_conv.backward_data(self.tf_pre.g[t], self.h_last.g[t], beta=1)
             if not self.merge_heads:
                 nb_last = None
@@ -968,7 +981,7 @@ class SAVPGenerator(object):
                 if L['rnn'] and self.abl_rnn:
                     a, n2 = L['a'], L['n2']
                     norm_bwd(n2, L['pre2'].v[t], self._out_views(L, t)[0], n2.mean[t], n2.rstd[t], dys, L['pre2'].g[t],
-                                       n2.dgamma, n2.dbeta, act='relu', eps=EPS_IN)
+                                       n2.dgamma, n2.dbeta, act=self.act, eps=EPS_IN)
                     L['rconv'].backward_data(L['pre2'].g[t], a.g[t], beta=0)
                     self._in_act_conv_bwd(L, t, a.v[t][..., 0:f], [a.g[t][..., 0:f]], None)
                     continue
@@ -988,7 +1001,7 @@ class SAVPGenerator(object):
                                         eps=EPS_IN)
                     L['rconv'].backward_data(L['gates'].g[t], a.g[t][..., 0:cin1], beta=1)
                     norm_bwd(nrm, L['pre'].v[t], a.v[t][..., 0:f], nrm.mean[t], nrm.rstd[t],
-                                       [a.g[t][..., 0:f]], L['pre'].g[t], nrm.dgamma, nrm.dbeta, act='relu', eps=EPS_IN)
+                                       [a.g[t][..., 0:f]], L['pre'].g[t], nrm.dgamma, nrm.dbeta, act=self.act, eps=EPS_IN)
                 elif L['rnn'] and self.cell_plain:
                     a = L['a']
                     if self.out_norm:

@@ -23,6 +23,26 @@ VIDEO_D_LAYERS = [  # (scope, ndf multiplier, kernel, strides(d,h,w))   networks
 # default variable scope of each normalizer_fn (ops.get_norm_layer, ops.py:1062-1074): fused_instance_norm -> 'InstanceNorm'
 # (layers/normalization.py:94), tf.contrib.layers.layer_norm -> 'LayerNorm'; 'none' is tf.identity (no variables)
 NORM_SCOPES = {'instance': 'InstanceNorm/', 'layer': 'LayerNorm/'}
+# variable scope of each down / upsample layer of the generator (ops.get_downsample_layer / get_upsample_layer, ops.py:1077-1098).  The _v2
+# layers compute what the un-suffixed ones compute (conv then average pool, ops.py:859-892; bilinear upsampling then conv, :722-761)
+# and create their variables under the un-suffixed scopes: aliases.
+DOWN_SCOPES = {'conv_pool2d': 'conv_pool2d', 'conv_pool2d_v2': 'conv_pool2d', 'conv2d': 'conv2d'}
+UP_SCOPES = {'upsample_conv2d': 'upsample_conv2d', 'upsample_conv2d_v2': 'upsample_conv2d', 'deconv2d': 'deconv2d'}
+ACTIVATIONS = ('relu', 'elu')            # ops.get_activation_layer, ops.py:1052-1059 (the generator only)
+
+
+def down_scope(hp):
+    if hp.downsample_layer not in DOWN_SCOPES:
+        raise ValueError('Invalid downsampling layer %s' % hp.downsample_layer)
+    return DOWN_SCOPES[hp.downsample_layer]
+
+
+def up_scope(hp):
+    if hp.upsample_layer not in UP_SCOPES:
+        raise ValueError('Invalid upsampling layer %s' % hp.upsample_layer)
+    return UP_SCOPES[hp.upsample_layer]
+
+
 IMAGE_D_LAYERS = [  # networks.py:45-64
     ('sn_conv0_0', 1, 3, 1), ('sn_conv0_1', 2, 4, 2), ('sn_conv1_0', 2, 3, 1), ('sn_conv1_1', 4, 4, 2),
     ('sn_conv2_0', 4, 3, 1), ('sn_conv2_1', 8, 4, 2), ('sn_conv3_0', 8, 3, 1),
@@ -199,8 +219,9 @@ def generator_variable_specs(hp, image_shape, cond=(0, 0)):
         cx = 2 * C if i == 0 else prev
         k = 5 if i == 0 else 3
         add_z = bool(zw) and (hp.where_add == 'all' or (hp.where_add == 'input' and i == 0))
-        specs[s + 'conv_pool2d/kernel'] = ((k, k, cx + (zc if add_z else 0), f), 'tn0.02')
-        specs[s + 'conv_pool2d/bias'] = ((f,), 'zeros')
+        op = down_scope(hp)
+        specs[s + op + '/kernel'] = ((k, k, cx + (zc if add_z else 0), f), 'tn0.02')
+        specs[s + op + '/bias'] = ((f,), 'zeros')
         if add_z and not tile:
             specs[s + 'dense/kernel'] = ((zw, f), 'tn0.02')
         norm(s, f)
@@ -214,8 +235,11 @@ def generator_variable_specs(hp, image_shape, cond=(0, 0)):
         s = p + 'h%d/' % li
         cx = prev if i == 0 else prev + layer_out[ne - i - 1]
         add_z = bool(zw) and (hp.where_add == 'all' or (hp.where_add == 'middle' and i == 0))
-        specs[s + 'upsample_conv2d/kernel'] = ((3, 3, cx + (zc if add_z else 0), f), 'tn0.02')
-        specs[s + 'upsample_conv2d/bias'] = ((f,), 'zeros')
+        op = up_scope(hp)
+        # deconv2d's kernel is the conv2d_transpose filter: output channels BEFORE input channels (ops.py:566)
+        cin = cx + (zc if add_z else 0)
+        specs[s + op + '/kernel'] = ((3, 3, f, cin) if op == 'deconv2d' else (3, 3, cin, f), 'tn0.02')
+        specs[s + op + '/bias'] = ((f,), 'zeros')
         if add_z and not tile:
             specs[s + 'dense/kernel'] = ((zw, f), 'tn0.02')
         norm(s, f)
