@@ -627,6 +627,13 @@ int savp_convgru_gates_bwd(void* stream, const SavpGruArgs* a);
 /* uint8 frames [B, T, frame] -> float32 time-major [T, B, frame] * (1/255): tf.image.convert_image_dtype (base_dataset.py:187)
  * + transpose_batch_time (tf_utils.py:118-122) for batches delivered by libsavp_io.so (include/savp_io.h); frame % 4 == 0 */
 int savp_u8_frames_to_f32(void* stream, const uint8_t* in, float* out, int32_t B, int32_t T, int64_t frame);
+/* input_resize.hip: the same conversion with the dataset hyper-parameters crop_size / scale_size (base_dataset.py:159-184) fused in.
+ * in: uint8 [B, T, Hs, Ws, C]; out: float32 time-major [T, B, S, S, C], every element written.  Per frame: centre crop or zero pad to
+ * crop x crop (tf.image.resize_image_with_crop_or_pad), then crop < S: TF1 bilinear (align_corners=False, no half-pixel offset),
+ * crop > S: TF resize_area, crop == S: unchanged; then * (1/255).  Source positions and weights come from the integers o * crop / S and
+ * o * crop % S; the weighted sum is exact (uint32) and rounded at the end.  1 <= crop, S <= 4096; out 4-byte aligned (16 for float4 stores). */
+int savp_u8_frames_resize_f32(void* stream, const uint8_t* in, float* out, int32_t B, int32_t T, int32_t Hs, int32_t Ws, int32_t C,
+                              int32_t crop, int32_t S);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Evaluation metrics and the best-of-N sampling fold (metrics.hip).  Time-major [T, B, ...] tensors with

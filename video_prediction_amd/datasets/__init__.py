@@ -1,6 +1,7 @@
 """Datasets with the reference's class API (video_prediction/datasets/__init__.py:9-24) on the C++ input pipeline."""
 from .softmotion_dataset import SoftmotionVideoDataset
 from .kth_dataset import KTHVideoDataset
+from .cartgripper_dataset import CartgripperVideoDataset
 
 
 def get_dataset_class(dataset):
@@ -9,6 +10,7 @@ def get_dataset_class(dataset):
         'softmotion': 'SoftmotionVideoDataset',
         'softmotion30_v1': 'SoftmotionVideoDataset',
         'kth': 'KTHVideoDataset',
+        'cartgripper': 'CartgripperVideoDataset',
     }
     dataset_class = dataset_mappings.get(dataset, dataset)
     dataset_class = globals().get(dataset_class)

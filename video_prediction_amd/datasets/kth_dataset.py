@@ -4,7 +4,8 @@ base_dataset.py:394-453 VarLenFeatureVideoDataset) on libsavp_io.so.
 Record layout (written by the reference's own preprocessing, kth_dataset.py:60-100): ONE tf.train.Example per sequence with int64
 features 'sequence_length', 'height', 'width', 'channels' and a bytes_list 'images/encoded' holding one raw uint8 frame per entry
 (jpeg_encoding False, :39-41).  Sequences shorter than hparams.sequence_length are dropped (filter, base_dataset.py:401-407); the
-sub-sequence is sampled per example (slice_sequences, :189-229) -- both inside the C++ pipeline (SavpVideoPipelineArgs.var_len)."""
+sub-sequence is sampled per example (slice_sequences, :189-229) -- both inside the C++ pipeline (SavpVideoPipelineArgs.var_len).
+crop_size / scale_size: as in softmotion_dataset.py (on the device, [0, 1] output)."""
 import glob
 import itertools
 import os
@@ -46,8 +47,6 @@ class KTHVideoDataset(SoftmotionVideoDataset):
         self.action_like_names_and_shapes = {}
         if self.hparams.use_state:
             raise NotImplementedError('KTH records carry no states / actions')
-        if self.hparams.crop_size or self.hparams.scale_size:
-            raise NotImplementedError('crop_size / scale_size are not supported by the HIP input path')
 
     def get_default_hparams_dict(self):
         """base_dataset.py:60-101 + kth_dataset.py:26-36."""

@@ -1,8 +1,19 @@
 """SoftmotionVideoDataset (BAIR robot pushing) with the reference's class surface
 (video_prediction/datasets/softmotion_dataset.py:11-82, base_dataset.py:12-232,235-353) on libsavp_io.so:
 C++ TFRecord reading / Example parsing / sub-sequence sampling / shuffling / batching / prefetch, uint8 over PCIe,
-conversion to float32 [0,1] on the GPU.  Not supported (raise): crop_size / scale_size (resizing), jpeg encoding, object_pos
-pixel distributions."""
+conversion to float32 [0,1] on the GPU.  Not supported (raise): jpeg encoding, object_pos pixel distributions.
+
+crop_size / scale_size (base_dataset.py:63-64,85-86,159-184).  The records are read and cross PCIe at the size they were recorded
+(image_shape); when either hyper-parameter is set the conversion kernel also centre-crops or zero-pads every frame to crop x crop
+(crop = crop_size or min(H, W); tf.image.resize_image_with_crop_or_pad) and resizes it to scale_size (smaller crop: TF1 bilinear,
+align_corners=False, no half-pixel offset; larger crop: TF resize_area), so that batch['images'] is [B, T, S, S, C] with
+(S, S, C) = output_image_shape (savp_u8_frames_resize_f32, include/savp_hip.h).  Two deliberate differences from the reference:
+  * Range.  The reference's resize ops return float32 in [0, 255] and its convert_image_dtype(float32) then leaves a float input alone,
+    so a resized batch would reach the model 255 times too large (no published recipe sets scale_size).  Here a batch is
+    resize(image) / 255, in [0, 1] in every case; resizing is linear, so this is the reference's tensor divided by 255.
+  * Coordinates.  Source positions and weights are taken from the integers (y * crop) / S and (y * crop) % S, not from TF's float32-rounded
+    scale; the two differ by a few 1e-6 of a pixel value at most for non-dyadic ratios, far below the uint8 step, and the result is exact.
+The reference reshapes to 3 channels; here any channel count the records carry (KTH may hold 1)."""
 import glob
 import itertools
 import os
@@ -17,6 +28,36 @@ from ..hparams import HParams
 
 class SoftmotionVideoDataset(object):
     def __init__(self, input_dir, mode='train', num_epochs=None, seed=None, hparams_dict=None, hparams=None):
+        self._open(input_dir, mode, num_epochs, seed, hparams_dict, hparams)
+        # infer the image feature name, frames per example and image shape from the first example (softmotion_dataset.py:15-43,
+        # base_dataset.py:264-312)
+        first = self._first
+        names = self._feature_names(first)
+        image_names = set(m.group(1) for m in (re.search(r'\d+/(\w+)/encoded', n) for n in names) if m)
+        image_name = next((n for n in ('image_aux1', 'image_view0') if n in image_names), None)
+        if not image_name:
+            if len(image_names) == 1:
+                image_name = image_names.pop()
+            else:
+                raise ValueError('The examples have images under more than one name.')
+        self.image_key_fmt = '%%d/%s/encoded' % image_name
+        self._max_sequence_length = self._count_frames(names, image_name)
+        _, buf = sio.example_feature(first, self.image_key_fmt % 0)
+        side = int(round((len(buf) // 3) ** 0.5))
+        if side * side * 3 != len(buf):
+            raise ValueError('cannot infer a square RGB image shape from %d bytes' % len(buf))
+        self.image_shape = (side, side, 3)
+        self.state_like_names_and_shapes = {'images': (self.image_key_fmt, self.image_shape)}
+        self.action_like_names_and_shapes = {}
+        if self.hparams.use_state:
+            self.state_like_names_and_shapes['states'] = ('%d/endeffector_pos', (3,))
+            self.action_like_names_and_shapes['actions'] = ('%d/action', (4,))
+
+    @staticmethod
+    def _count_frames(names, image_name):
+        return 1 + max(int(m.group(1)) for m in (re.match(r'(\d+)/%s/encoded' % image_name, n) for n in names) if m)
+
+    def _open(self, input_dir, mode, num_epochs, seed, hparams_dict, hparams):
         """base_dataset.py:13-58: input_dir holds train/ val/ test/ sub-directories of *.tfrecord* files (or is one of them)."""
         self.input_dir = os.path.normpath(os.path.expanduser(input_dir))
         self.mode = mode
@@ -38,32 +79,22 @@ class SoftmotionVideoDataset(object):
             raise FileNotFoundError('No tfrecords were found in %s.' % self.input_dir)
         self.dataset_name = os.path.basename(os.path.split(self.input_dir)[0])
         self.hparams = self.parse_hparams(hparams_dict, hparams)
-        # infer the image feature name, frames per example and image shape from the first example (softmotion_dataset.py:15-43,
-        # base_dataset.py:264-312)
-        first = sio.read_records(self.filenames[0])[0]
-        self._first = first
-        names = self._feature_names(first)
-        image_names = set(m.group(1) for m in (re.search(r'\d+/(\w+)/encoded', n) for n in names) if m)
-        image_name = next((n for n in ('image_aux1', 'image_view0') if n in image_names), None)
-        if not image_name:
-            if len(image_names) == 1:
-                image_name = image_names.pop()
-            else:
-                raise ValueError('The examples have images under more than one name.')
-        self.image_key_fmt = '%%d/%s/encoded' % image_name
-        self._max_sequence_length = 1 + max(int(m.group(1)) for m in (re.match(r'(\d+)/%s/encoded' % image_name, n) for n in names) if m)
-        _, buf = sio.example_feature(first, self.image_key_fmt % 0)
-        side = int(round((len(buf) // 3) ** 0.5))
-        if side * side * 3 != len(buf):
-            raise ValueError('cannot infer a square RGB image shape from %d bytes' % len(buf))
-        self.image_shape = (side, side, 3)
-        self.state_like_names_and_shapes = {'images': (self.image_key_fmt, self.image_shape)}
-        self.action_like_names_and_shapes = {}
-        if self.hparams.use_state:
-            self.state_like_names_and_shapes['states'] = ('%d/endeffector_pos', (3,))
-            self.action_like_names_and_shapes['actions'] = ('%d/action', (4,))
-        if self.hparams.crop_size or self.hparams.scale_size:
-            raise NotImplementedError('crop_size / scale_size are not supported by the HIP input path')
+        self._first = sio.read_records(self.filenames[0])[0]
+
+    @property
+    def crop_and_scale(self):
+        """(crop, S) of base_dataset.py:166-183 when crop_size or scale_size is set, else None (frames are delivered as recorded)."""
+        hp = self.hparams
+        if not (hp.crop_size or hp.scale_size):
+            return None
+        crop = hp.crop_size or min(self.image_shape[:2])
+        return crop, (hp.scale_size or crop)
+
+    @property
+    def output_image_shape(self):
+        """Frame shape of batch['images'] -- what the model is sized from; image_shape stays the shape of the records."""
+        cs = self.crop_and_scale
+        return tuple(self.image_shape) if cs is None else (cs[1], cs[1], self.image_shape[2])
 
     @staticmethod
     def _feature_names(example):
@@ -140,7 +171,8 @@ class SoftmotionVideoDataset(object):
         time_shift = hp.time_shift if ((hp.time_shift and self.mode == 'train') or hp.force_time_shift) else 0   # :198
         float_keys = []
         if hp.use_state:
-            float_keys = [('%d/endeffector_pos', 3, 0), ('%d/action', 4, 1)]
+            (s_fmt, s_shape), (a_fmt, a_shape) = self.state_like_names_and_shapes['states'], self.action_like_names_and_shapes['actions']
+            float_keys = [(s_fmt, s_shape[0], 0), (a_fmt, a_shape[0], 1)]
         files, seed = self._shard(rank, world)
         return sio.VideoPipeline(files, self.image_key_fmt, self._max_sequence_length, self.image_shape,
                                  hp.sequence_length, batch_size, frame_skip=hp.frame_skip, time_shift=time_shift, shuffle=shuffle,
@@ -186,8 +218,12 @@ class _BatchIterator(object):
             self.copied = torch.cuda.Event()
             self.copied.record(torch.cuda.current_stream(self.device))
         B, T = self.dev_u8.shape[:2]
-        images_tm = torch.empty((T, B) + self.ds.image_shape, device=self.device)
-        self.K.u8_frames_to_f32(self.dev_u8, images_tm)
+        images_tm = torch.empty((T, B) + self.ds.output_image_shape, device=self.device)
+        cs = self.ds.crop_and_scale
+        if cs is None:
+            self.K.u8_frames_to_f32(self.dev_u8, images_tm)
+        else:
+            self.K.u8_frames_resize_f32(self.dev_u8, images_tm, cs[0])
         out = {'images': images_tm.transpose(0, 1)}                      # batch-major view, like the reference's iterator
         if floats:
             out['states'] = torch.from_numpy(floats[0]).to(self.device)

@@ -1675,6 +1675,23 @@ def u8_frames_to_f32(frames_u8, out_tm):
     lib.check(_L().savp_u8_frames_to_f32(lib.stream(), frames_u8.data_ptr(), out_tm.data_ptr(), B, T, frame), 'savp_u8_frames_to_f32')
 
 
+def u8_frames_resize_f32(frames_u8, out_tm, crop):
+    """uint8 [B, T, Hs, Ws, C] -> float32 time-major [T, B, S, S, C] in [0, 1]: every frame centre-cropped or zero-padded to crop x crop,
+    then resized to the S x S of out_tm (crop < S: TF1 bilinear, crop > S: TF area, crop == S: unchanged) and divided by 255
+    (base_dataset.py:159-184 + transpose_batch_time; include/savp_hip.h)."""
+    lib.require_device(out_tm)
+    if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()):
+        raise RuntimeError('expected a contiguous uint8 device tensor')
+    if frames_u8.dim() != 5 or out_tm.dim() != 5 or not out_tm.is_contiguous():
+        raise ValueError('u8_frames_resize_f32: frames [B, T, Hs, Ws, C] and a contiguous output [T, B, S, S, C] expected')
+    B, T, Hs, Ws, C = frames_u8.shape
+    S = out_tm.shape[2]
+    if tuple(out_tm.shape) != (T, B, S, S, C):
+        raise ValueError('u8_frames_resize_f32: output %r does not fit frames %r' % (tuple(out_tm.shape), tuple(frames_u8.shape)))
+    lib.check(_L().savp_u8_frames_resize_f32(lib.stream(), frames_u8.data_ptr(), out_tm.data_ptr(), B, T, Hs, Ws, C, int(crop), S),
+              'savp_u8_frames_resize_f32')
+
+
 class KernelTimer(object):
     """Kernel-only timing of single instrumented launches (bench.py): event pairs handed to the launcher through savp_prof_arm,
     stamped by the dispatch itself (the duration rocprofv3's kernel trace reports).  arm() before the launch, taken() after it
