@@ -635,6 +635,29 @@ int savp_u8_frames_to_f32(void* stream, const uint8_t* in, float* out, int32_t B
 int savp_u8_frames_resize_f32(void* stream, const uint8_t* in, float* out, int32_t B, int32_t T, int32_t Hs, int32_t Ws, int32_t C,
                               int32_t crop, int32_t S);
 
+/* jpeg_decode.hip: the device half of JPEG decoding (tf.image.decode_jpeg, base_dataset.py:161-162; decode_and_crop_jpeg,
+ * ucf101_dataset.py:48) for N frames of one geometry whose Huffman bitstreams were decoded on the host (savp_jpeg_entropy_decode,
+ * savp_io.h; the geometry fields are SavpJpegInfo's).  Dequantisation, the jidctint "islow" IDCT, cropping of the planes, libjpeg's fancy
+ * chroma upsampling and YCbCr -> RGB in libjpeg's integer arithmetic: the output equals libjpeg-turbo's (dct_method default,
+ * fancy_upscaling=True) sample for sample.  components 1 or 3, chroma 1x1 with luma 1x1 / 2x1 / 2x2; anything else, or a geometry that is
+ * not consistent with itself, returns SAVP_EINVAL without a launch.  Every byte of out is written; MCU padding never is.
+ * window NULL: out_h x out_w must be height x width.  Otherwise frame n delivers the out_h x out_w window at (y0, x0) = window[n]
+ * (device memory; clamped into the image).  ws: savp_jpeg_workspace_bytes() bytes of device memory for the component planes, 8-byte
+ * aligned; coef and qtab 16-byte aligned. */
+typedef struct SavpJpegArgs {
+    int32_t N;
+    int32_t width, height, components;
+    int32_t h[3], v[3], blocks_w[3], blocks_h[3], block_offset[3], total_blocks;
+    int32_t out_h, out_w;
+    const int16_t* coef;             /* [N, total_blocks, 64] row-major inside a block, not dequantised */
+    const uint16_t* qtab;            /* [N, components, 64] */
+    const int32_t* window;           /* [N, 2] or NULL */
+    uint8_t* out;                    /* [N, out_h, out_w, components] */
+    void* ws; int64_t ws_bytes;
+} SavpJpegArgs;
+int savp_jpeg_decode_u8(void* stream, const SavpJpegArgs* a);
+int64_t savp_jpeg_workspace_bytes(const SavpJpegArgs* a);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Evaluation metrics and the best-of-N sampling fold (metrics.hip).  Time-major [T, B, ...] tensors with
  * explicit element strides (x_st = time, x_sb = batch); frames are contiguous (H*W*C floats).

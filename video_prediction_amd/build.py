@@ -54,11 +54,11 @@ def build(force=False, verbose=False):
 
 def build_io(force=False, verbose=False):
     """libsavp_io.so: the host-side C++ input pipeline (include/savp_io.h), plain g++."""
-    src = os.path.join(HERE, 'csrc_host', 'tfrecord_pipeline.cpp')
+    srcs = [os.path.join(HERE, 'csrc_host', f) for f in ('tfrecord_pipeline.cpp', 'jpeg_decode.cpp')]
     out = os.path.join(HERE, 'libsavp_io.so')
     hdr = os.path.join(INCLUDE, 'savp_io.h')
-    if force or _newer(src, out, (hdr,)):
-        cmd = [os.environ.get('CXX', 'g++'), '-O2', '-std=c++17', '-fPIC', '-shared', '-pthread', '-I' + INCLUDE, src, '-o', out]
+    if force or _newer(srcs[0], out, (hdr,) + tuple(srcs[1:])):
+        cmd = [os.environ.get('CXX', 'g++'), '-O2', '-std=c++17', '-fPIC', '-shared', '-pthread', '-I' + INCLUDE] + srcs + ['-o', out]
         if verbose:
             print(' '.join(cmd), flush=True)
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -6,8 +6,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -262,7 +265,51 @@ struct Rng {                                                               // sp
 
 struct FloatKey { std::string fmt; int dim; int minus; };
 
-struct Batch { std::vector<uint8_t> images; std::vector<std::vector<float>> floats; };
+struct Batch {
+    std::vector<uint8_t> images; std::vector<std::vector<float>> floats;
+    // jpeg pipelines (images stays empty).  coef is left uninitialised here: every frame's slice is cleared by the worker that decodes it
+    std::unique_ptr<int16_t[]> coef; size_t coef_n = 0; std::vector<uint16_t> qtab; std::vector<int32_t> windows;
+};
+
+struct Record { std::vector<uint8_t> data; int file; };                   // one serialized Example and the index of the file it came from
+
+// Fixed set of worker threads that run the entropy decoding of one example's frames; run() returns when every job has finished.
+struct WorkerPool {
+    std::vector<std::thread> th;
+    std::mutex mu;
+    std::condition_variable cv_work, cv_done;
+    const std::function<void(int)>* job = nullptr;
+    int next = 0, total = 0, pending = 0;
+    bool stop = false;
+    explicit WorkerPool(int n) {
+        for (int i = 0; i < n; ++i) th.emplace_back([this] { loop(); });
+    }
+    ~WorkerPool() {
+        { std::lock_guard<std::mutex> l(mu); stop = true; }
+        cv_work.notify_all();
+        for (std::thread& t : th) t.join();
+    }
+    void loop() {
+        std::unique_lock<std::mutex> l(mu);
+        for (;;) {
+            cv_work.wait(l, [&] { return stop || next < total; });
+            if (stop) return;
+            const int i = next++;
+            const std::function<void(int)>* f = job;
+            l.unlock();
+            (*f)(i);
+            l.lock();
+            if (--pending == 0) cv_done.notify_all();
+        }
+    }
+    void run(int n, const std::function<void(int)>& f) {
+        std::unique_lock<std::mutex> l(mu);
+        job = &f; next = 0; total = n; pending = n;
+        cv_work.notify_all();
+        cv_done.wait(l, [&] { return pending == 0; });
+        total = 0; job = nullptr;
+    }
+};
 }  // namespace
 
 struct SavpVideoPipeline {
@@ -272,6 +319,9 @@ struct SavpVideoPipeline {
     int example_frames, H, W, C, seq, frame_skip, time_shift, batch, shuffle, shuffle_buffer, num_epochs, prefetch;
     int var_len = 0;                  // 1: one bytes_list feature holds all frames of a sequence + int64 'sequence_length' (KTH)
     uint64_t seed;
+    int jpeg = 0, decode_threads = 0, random_crop = 0;   // jpeg: the image features are JPEG streams, entropy-decoded on decode_threads workers
+    SavpJpegInfo jinfo;                                  // geometry of the first frame of the first example; every frame must share it
+    std::unique_ptr<WorkerPool> workers;
 
     std::thread th;
     std::mutex mu;
@@ -289,7 +339,7 @@ struct SavpVideoPipeline {
 
     // decode one serialized Example into the slot `b` of the batch under construction; SKIP = filtered out (too short, var_len only)
     enum { SKIP = 1 };
-    int decode(const std::vector<uint8_t>& ex, Rng& rng, Batch& out, int b) {
+    int decode(const std::vector<uint8_t>& ex, int file, Rng& rng, Batch& out, int b) {
         const int fs1 = frame_skip + 1;
         int frames = example_frames;
         if (var_len) {                                                     // VarLenFeatureVideoDataset.filter / parser (base_dataset.py:401-429)
@@ -307,8 +357,13 @@ struct SavpVideoPipeline {
         } else if ((seq - 1) * fs1 + 1 > frames) {
             errmsg = "example_sequence_length too short for sequence_length / frame_skip"; return SAVP_IO_EINVAL;
         }
+        if (random_crop > 0) {                                             // ucf101_dataset.py:43-47: one window per sequence, maxval exclusive
+            out.windows[2 * b] = (int32_t)rng.below((uint64_t)(jinfo.height - random_crop));
+            out.windows[2 * b + 1] = (int32_t)rng.below((uint64_t)(jinfo.width - random_crop));
+        }
         const size_t frame = (size_t)H * W * C;
         char name[256];
+        std::vector<Span> streams((size_t)(jpeg ? seq : 0));
         for (int t = 0; t < seq; ++t) {                                    // state-like slice (:213)
             const int src_t = t_start + t * fs1;
             if (var_len) snprintf(name, sizeof(name), "%s", image_fmt.c_str());
@@ -316,8 +371,30 @@ struct SavpVideoPipeline {
             int32_t kind; const uint8_t* p; uint64_t n;
             int rc = savp_example_feature(ex.data(), ex.size(), name, var_len ? src_t : 0, &kind, &p, &n);
             if (rc) { errmsg = std::string("feature ") + name + (rc == SAVP_IO_EMISSING ? " not found in tfrecord" : " is corrupt"); return rc; }
+            if (jpeg) {
+                if (kind != 1) { errmsg = std::string("feature ") + name + ": expected one JPEG stream"; return SAVP_IO_EINVAL; }
+                streams[(size_t)t] = Span{p, n};
+                continue;
+            }
             if (kind != 1 || n != frame) { errmsg = std::string("feature ") + name + ": expected one raw uint8 image of H*W*C bytes"; return SAVP_IO_EINVAL; }
             memcpy(out.images.data() + ((size_t)b * seq + t) * frame, p, frame);
+        }
+        if (jpeg) {                                                        // only the frames that survived the sampling are decoded
+            const size_t cf = (size_t)jinfo.total_blocks * 64, qf = (size_t)jinfo.components * 64;
+            std::vector<int> rcs((size_t)seq, 0);
+            std::vector<std::string> msgs((size_t)seq);
+            const std::function<void(int)> one = [&](int t) {
+                const size_t slot = (size_t)b * seq + t;
+                rcs[(size_t)t] = savp_jpeg_entropy_decode(streams[(size_t)t].p, streams[(size_t)t].n, &jinfo, out.coef.get() + slot * cf,
+                                                          out.qtab.data() + slot * qf);
+                if (rcs[(size_t)t]) msgs[(size_t)t] = savp_jpeg_error();   // the message lives in the worker's thread
+            };
+            workers->run(seq, one);
+            for (int t = 0; t < seq; ++t)
+                if (rcs[(size_t)t]) {
+                    errmsg = "frame " + std::to_string(t_start + t * fs1) + " of an example in " + files[(size_t)file] + ": " + msgs[(size_t)t];
+                    return rcs[(size_t)t];
+                }
         }
         for (size_t k = 0; k < fkeys.size(); ++k) {
             const FloatKey& fk = fkeys[k];
@@ -339,9 +416,39 @@ struct SavpVideoPipeline {
         return SAVP_IO_OK;
     }
 
+    // jpeg: geometry of the first frame of the first example of the first file (what the reference takes its shapes from)
+    int first_geometry() {
+        SavpTfrFile* f = nullptr;
+        if (savp_tfr_open(files[0].c_str(), 8 << 20, &f)) { errmsg = "cannot open " + files[0]; return SAVP_IO_EIO; }
+        const uint8_t* d; uint64_t n;
+        int rc = savp_tfr_next(f, &d, &n);
+        if (rc == SAVP_IO_OK) {
+            char name[256];
+            if (var_len) snprintf(name, sizeof(name), "%s", image_fmt.c_str());
+            else snprintf(name, sizeof(name), image_fmt.c_str(), 0);
+            int32_t kind; const uint8_t* p; uint64_t pn;
+            rc = savp_example_feature(d, n, name, 0, &kind, &p, &pn);
+            if (rc == SAVP_IO_OK && kind != 1) rc = SAVP_IO_EINVAL;
+            if (rc) errmsg = std::string("feature ") + name + " not found as a bytes feature in " + files[0];
+            else if ((rc = savp_jpeg_info(p, pn, &jinfo)) != 0) errmsg = files[0] + ": " + savp_jpeg_error();
+        } else {
+            errmsg = "no readable record in " + files[0];
+            if (rc == SAVP_IO_EOF) rc = SAVP_IO_ECORRUPT;
+        }
+        savp_tfr_close(f);
+        return rc;
+    }
+
     Batch new_batch() const {
         Batch bt;
-        bt.images.resize((size_t)batch * seq * H * W * C);
+        if (jpeg) {
+            bt.coef_n = (size_t)batch * seq * jinfo.total_blocks * 64;
+            bt.coef.reset(new int16_t[bt.coef_n]);
+            bt.qtab.resize((size_t)batch * seq * jinfo.components * 64);
+            bt.windows.assign((size_t)batch * 2, 0);
+        } else {
+            bt.images.resize((size_t)batch * seq * H * W * C);
+        }
         bt.floats.resize(fkeys.size());
         for (size_t k = 0; k < fkeys.size(); ++k)
             bt.floats[k].resize(fkeys[k].minus == 0 ? (size_t)batch * seq * fkeys[k].dim
@@ -351,16 +458,16 @@ struct SavpVideoPipeline {
 
     void run() {
         Rng rng(seed ? seed : 0x5eedull);
-        std::vector<std::string> order = files;
+        std::vector<int> order(files.size());
+        for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
         if (shuffle)                                                       // random.shuffle(filenames), base_dataset.py:132-133
             for (size_t i = order.size(); i > 1; --i) std::swap(order[i - 1], order[rng.below(i)]);
-        std::vector<std::vector<uint8_t>> pool;                            // shuffle buffer (:137-138)
+        std::vector<Record> pool;                            // shuffle buffer (:137-138)
         const size_t cap = shuffle ? (size_t)(shuffle_buffer > 0 ? shuffle_buffer : 1024) : 1;
         Batch cur = new_batch();
         int filled = 0;
-        auto emit = [&](const std::vector<uint8_t>& ex) -> bool {
-            std::string msg;
-            int rc = decode(ex, rng, cur, filled);
+        auto emit = [&](const Record& ex) -> bool {
+            int rc = decode(ex.data, ex.file, rng, cur, filled);
             if (rc == SKIP) return true;
             if (rc) { fail(rc, errmsg); return false; }
             if (++filled == batch) {
@@ -375,7 +482,8 @@ struct SavpVideoPipeline {
             return true;
         };
         for (int epoch = 0; num_epochs <= 0 || epoch < num_epochs; ++epoch) {
-            for (const std::string& path : order) {
+            for (const int file : order) {
+                const std::string& path = files[(size_t)file];
                 SavpTfrFile* f = nullptr;
                 if (savp_tfr_open(path.c_str(), 8 << 20, &f)) { fail(SAVP_IO_EIO, "cannot open " + path); return; }
                 for (;;) {
@@ -384,17 +492,17 @@ struct SavpVideoPipeline {
                     if (rc == SAVP_IO_EOF) break;
                     if (rc) { savp_tfr_close(f); fail(rc, "corrupt record in " + path); return; }
                     { std::lock_guard<std::mutex> l(mu); if (stop) { savp_tfr_close(f); return; } }
-                    if (pool.size() < cap) { pool.emplace_back(d, d + n); if (pool.size() < cap) continue; }
+                    if (pool.size() < cap) { pool.push_back(Record{std::vector<uint8_t>(d, d + n), file}); if (pool.size() < cap) continue; }
                     else {
                         // buffer full: emit a random element and put the new record in its place
                         const size_t i = shuffle ? (size_t)rng.below(pool.size()) : 0;
-                        std::vector<uint8_t> ex(d, d + n);
+                        Record ex{std::vector<uint8_t>(d, d + n), file};
                         std::swap(ex, pool[i]);
                         if (!emit(ex)) { savp_tfr_close(f); return; }
                         continue;
                     }
                     if (!shuffle) {                                         // cap == 1: emit in file order
-                        std::vector<uint8_t> ex; std::swap(ex, pool[0]); pool.clear();
+                        Record ex; std::swap(ex, pool[0]); pool.clear();
                         if (!emit(ex)) { savp_tfr_close(f); return; }
                     }
                 }
@@ -403,7 +511,7 @@ struct SavpVideoPipeline {
         }
         while (!pool.empty()) {                                            // drain the shuffle buffer at the end of the last epoch
             const size_t i = shuffle ? (size_t)rng.below(pool.size()) : 0;
-            std::vector<uint8_t> ex; std::swap(ex, pool[i]);
+            Record ex; std::swap(ex, pool[i]);
             pool[i] = std::move(pool.back()); pool.pop_back();
             if (!emit(ex)) return;
         }
@@ -413,10 +521,14 @@ struct SavpVideoPipeline {
     }
 };
 
+static thread_local std::string g_create_error;
+extern "C" const char* savp_pipeline_create_error(void) { return g_create_error.c_str(); }
+
 extern "C" int savp_pipeline_create(const SavpVideoPipelineArgs* a, SavpVideoPipeline** out) {
     if (!a || !out || a->num_files < 1 || !a->filenames || !a->image_key_fmt || (a->example_frames < 1 && !a->var_len) || a->height < 1 ||
         a->width < 1 || a->channels < 1 || a->sequence_length < 1 || a->frame_skip < 0 || a->time_shift < 0 || a->batch_size < 1)
         return SAVP_IO_EINVAL;
+    if (a->decode_threads < 0 || a->random_crop < 0 || (a->random_crop > 0 && !a->jpeg)) return SAVP_IO_EINVAL;
     if (!a->var_len && (a->sequence_length - 1) * (a->frame_skip + 1) + 1 > a->example_frames) return SAVP_IO_EINVAL;
     SavpVideoPipeline* p = new SavpVideoPipeline();
     for (int i = 0; i < a->num_files; ++i) p->files.emplace_back(a->filenames[i]);
@@ -428,13 +540,23 @@ extern "C" int savp_pipeline_create(const SavpVideoPipelineArgs* a, SavpVideoPip
     p->shuffle = a->shuffle; p->shuffle_buffer = a->shuffle_buffer; p->num_epochs = a->num_epochs; p->seed = a->seed;
     p->prefetch = a->prefetch_batches > 0 ? a->prefetch_batches : 2;
     p->var_len = a->var_len ? 1 : 0;
+    p->jpeg = a->jpeg ? 1 : 0;
+    p->random_crop = a->random_crop;
+    if (p->jpeg) {
+        // worker count: the caller's, 4 by default, 16 at most -- never the machine's core count (a job is given its share of a host)
+        p->decode_threads = a->decode_threads > 0 ? (a->decode_threads > 16 ? 16 : a->decode_threads) : 4;
+        const int rc = p->first_geometry();
+        if (rc) { g_create_error = p->errmsg; delete p; return rc; }
+        if (p->random_crop > p->jinfo.height || p->random_crop > p->jinfo.width) { g_create_error = "random_crop exceeds the frames"; delete p; return SAVP_IO_EINVAL; }
+        p->workers.reset(new WorkerPool(p->decode_threads));
+    }
     p->th = std::thread([p] { p->run(); });
     *out = p;
     return SAVP_IO_OK;
 }
 
 extern "C" int savp_pipeline_next(SavpVideoPipeline* p, uint8_t* images, float* const* floats) {
-    if (!p || !images) return SAVP_IO_EINVAL;
+    if (!p || !images || p->jpeg) return SAVP_IO_EINVAL;
     Batch bt;
     {
         std::unique_lock<std::mutex> l(p->mu);
@@ -465,4 +587,29 @@ extern "C" void savp_pipeline_destroy(SavpVideoPipeline* p) {
     }
     if (p->th.joinable()) p->th.join();
     delete p;
+}
+
+extern "C" int savp_pipeline_jpeg_info(SavpVideoPipeline* p, SavpJpegInfo* out) {
+    if (!p || !out || !p->jpeg) return SAVP_IO_EINVAL;
+    *out = p->jinfo;
+    return SAVP_IO_OK;
+}
+
+extern "C" int savp_pipeline_next_jpeg(SavpVideoPipeline* p, int16_t* coef, uint16_t* qtab, int32_t* windows, float* const* floats) {
+    if (!p || !coef || !qtab || !p->jpeg || (p->random_crop > 0 && !windows)) return SAVP_IO_EINVAL;
+    Batch bt;
+    {
+        std::unique_lock<std::mutex> l(p->mu);
+        p->cv_ready.wait(l, [&] { return !p->ready.empty() || p->done; });
+        if (p->ready.empty()) return p->err ? p->err : SAVP_IO_EOF;
+        bt = std::move(p->ready.front());
+        p->ready.pop_front();
+        p->cv_space.notify_one();
+    }
+    memcpy(coef, bt.coef.get(), bt.coef_n * sizeof(int16_t));
+    memcpy(qtab, bt.qtab.data(), bt.qtab.size() * sizeof(uint16_t));
+    if (p->random_crop > 0) memcpy(windows, bt.windows.data(), bt.windows.size() * sizeof(int32_t));
+    for (size_t k = 0; k < bt.floats.size(); ++k)
+        if (floats && floats[k]) memcpy(floats[k], bt.floats[k].data(), bt.floats[k].size() * sizeof(float));
+    return SAVP_IO_OK;
 }

@@ -2,6 +2,9 @@
 from .softmotion_dataset import SoftmotionVideoDataset
 from .kth_dataset import KTHVideoDataset
 from .cartgripper_dataset import CartgripperVideoDataset
+from .google_robot_dataset import GoogleRobotVideoDataset
+from .sv2p_dataset import SV2PVideoDataset
+from .ucf101_dataset import UCF101VideoDataset
 
 
 def get_dataset_class(dataset):
@@ -11,6 +14,9 @@ def get_dataset_class(dataset):
         'softmotion30_v1': 'SoftmotionVideoDataset',
         'kth': 'KTHVideoDataset',
         'cartgripper': 'CartgripperVideoDataset',
+        'google_robot': 'GoogleRobotVideoDataset',
+        'sv2p': 'SV2PVideoDataset',
+        'ucf101': 'UCF101VideoDataset',
     }
     dataset_class = dataset_mappings.get(dataset, dataset)
     dataset_class = globals().get(dataset_class)

@@ -1,7 +1,8 @@
 """SoftmotionVideoDataset (BAIR robot pushing) with the reference's class surface
 (video_prediction/datasets/softmotion_dataset.py:11-82, base_dataset.py:12-232,235-353) on libsavp_io.so:
 C++ TFRecord reading / Example parsing / sub-sequence sampling / shuffling / batching / prefetch, uint8 over PCIe,
-conversion to float32 [0,1] on the GPU.  Not supported (raise): jpeg encoding, object_pos pixel distributions.
+conversion to float32 [0,1] on the GPU.  Frames here are raw uint8 (jpeg_encoding False); the JPEG-encoded datasets build on this class in
+jpeg_dataset.py.  Not supported (raise): object_pos pixel distributions.
 
 crop_size / scale_size (base_dataset.py:63-64,85-86,159-184).  The records are read and cross PCIe at the size they were recorded
 (image_shape); when either hyper-parameter is set the conversion kernel also centre-crops or zero-pads every frame to crop x crop

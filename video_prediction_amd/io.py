@@ -7,8 +7,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libsavp_io.so')
 
 c_i32, c_i64, c_u64, c_vp, c_cp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_char_p
-ERRORS = {-1: 'invalid argument', -2: 'I/O error', -3: 'corrupt record', -4: 'end of data', -5: 'feature not found'}
+ERRORS = {-1: 'invalid argument', -2: 'I/O error', -3: 'corrupt record', -4: 'end of data', -5: 'feature not found',
+          -6: 'unsupported stream'}
 EOF_CODE = -4
+EUNSUPPORTED, ECORRUPT = -6, -3
 
 
 class SavpVideoPipelineArgs(ctypes.Structure):
@@ -19,7 +21,27 @@ class SavpVideoPipelineArgs(ctypes.Structure):
         ('seed', c_u64), ('prefetch_batches', c_i32),
         ('float_keys_fmt', ctypes.POINTER(c_cp)), ('float_dims', ctypes.POINTER(c_i32)),
         ('float_per_frame_minus', ctypes.POINTER(c_i32)), ('num_float_keys', c_i32), ('var_len', c_i32),
+        ('jpeg', c_i32), ('decode_threads', c_i32), ('random_crop', c_i32),
     ]
+
+
+class SavpJpegInfo(ctypes.Structure):
+    _fields_ = [('width', c_i32), ('height', c_i32), ('components', c_i32), ('h', c_i32 * 3), ('v', c_i32 * 3), ('blocks_w', c_i32 * 3),
+                ('blocks_h', c_i32 * 3), ('block_offset', c_i32 * 3), ('total_blocks', c_i32)]
+
+    def as_dict(self):
+        n = self.components
+        d = {k: int(getattr(self, k)) for k in ('width', 'height', 'components', 'total_blocks')}
+        d.update({k: [int(x) for x in getattr(self, k)][:n] for k in ('h', 'v', 'blocks_w', 'blocks_h', 'block_offset')})
+        return d
+
+
+class JpegError(RuntimeError):
+    """A JPEG stream the host decoder refuses; code is SAVP_IO_EUNSUPPORTED (legal, not handled) or SAVP_IO_ECORRUPT."""
+
+    def __init__(self, code, message):
+        RuntimeError.__init__(self, '%s (%s, %d)' % (message, ERRORS.get(code, 'error'), code))
+        self.code = code
 
 
 _lib = None
@@ -46,6 +68,12 @@ def get():
         L.savp_pipeline_next.argtypes, L.savp_pipeline_next.restype = [c_vp, c_vp, P(c_vp)], c_i32
         L.savp_pipeline_error.argtypes, L.savp_pipeline_error.restype = [c_vp], c_cp
         L.savp_pipeline_destroy.argtypes, L.savp_pipeline_destroy.restype = [c_vp], None
+        L.savp_jpeg_info.argtypes, L.savp_jpeg_info.restype = [c_vp, c_u64, P(SavpJpegInfo)], c_i32
+        L.savp_jpeg_entropy_decode.argtypes, L.savp_jpeg_entropy_decode.restype = [c_vp, c_u64, P(SavpJpegInfo), c_vp, c_vp], c_i32
+        L.savp_jpeg_error.argtypes, L.savp_jpeg_error.restype = [], c_cp
+        L.savp_pipeline_jpeg_info.argtypes, L.savp_pipeline_jpeg_info.restype = [c_vp, P(SavpJpegInfo)], c_i32
+        L.savp_pipeline_next_jpeg.argtypes, L.savp_pipeline_next_jpeg.restype = [c_vp, c_vp, c_vp, c_vp, P(c_vp)], c_i32
+        L.savp_pipeline_create_error.argtypes, L.savp_pipeline_create_error.restype = [], c_cp
         _lib = L
     return _lib
 
@@ -105,13 +133,36 @@ def example_int64(example, name, index=0):
     return int(v.value)
 
 
+def jpeg_info(data):
+    """Geometry of a JPEG stream (headers only) as a SavpJpegInfo; raises JpegError."""
+    data = bytes(data)
+    out = SavpJpegInfo()
+    rc = get().savp_jpeg_info(data, len(data), ctypes.byref(out))
+    if rc:
+        raise JpegError(rc, get().savp_jpeg_error().decode())
+    return out
+
+
+def jpeg_entropy_decode(data, expect=None):
+    """(info, coef int16 [total_blocks, 64], qtab uint16 [components, 64]) of one JPEG stream: the host half of decoding."""
+    import numpy as np
+    data = bytes(data)
+    info = expect if expect is not None else jpeg_info(data)
+    coef = np.empty((info.total_blocks, 64), np.int16)
+    qtab = np.empty((info.components, 64), np.uint16)
+    rc = get().savp_jpeg_entropy_decode(data, len(data), ctypes.byref(info), coef.ctypes.data, qtab.ctypes.data)
+    if rc:
+        raise JpegError(rc, get().savp_jpeg_error().decode())
+    return info, coef, qtab
+
+
 class VideoPipeline(object):
     """Batched, shuffling, prefetching reader (one C++ thread): next() fills caller buffers with uint8 frames
     [B, T, H, W, C] and the optional float features."""
 
     def __init__(self, filenames, image_key_fmt, example_frames, image_shape, sequence_length, batch_size, frame_skip=0,
                  time_shift=0, shuffle=False, shuffle_buffer=1024, num_epochs=1, seed=0, prefetch_batches=2, float_keys=(),
-                 var_len=False):
+                 var_len=False, jpeg=False, decode_threads=0, random_crop=0):
         import numpy as np
         self._np = np
         L = get()
@@ -131,11 +182,21 @@ class VideoPipeline(object):
             self._fd = (c_i32 * len(self.float_keys))(*[k[1] for k in self.float_keys])
             self._fm = (c_i32 * len(self.float_keys))(*[k[2] for k in self.float_keys])
             a.float_keys_fmt, a.float_dims, a.float_per_frame_minus, a.num_float_keys = self._fk, self._fd, self._fm, len(self.float_keys)
+        a.jpeg, a.decode_threads, a.random_crop = int(bool(jpeg)), int(decode_threads), int(random_crop)
         self._args = a
         self.shape = (batch_size, sequence_length) + tuple(image_shape)
         self.frame_skip = frame_skip
+        self.jpeg, self.random_crop = bool(jpeg), int(random_crop)
         self._h = c_vp()
-        check(L.savp_pipeline_create(ctypes.byref(a), ctypes.byref(self._h)), 'savp_pipeline_create')
+        rc = L.savp_pipeline_create(ctypes.byref(a), ctypes.byref(self._h))
+        if rc and jpeg:
+            raise JpegError(rc, 'savp_pipeline_create: ' + L.savp_pipeline_create_error().decode())
+        check(rc, 'savp_pipeline_create')
+        if jpeg:
+            self.jpeg_info = SavpJpegInfo()
+            check(L.savp_pipeline_jpeg_info(self._h, ctypes.byref(self.jpeg_info)), 'savp_pipeline_jpeg_info')
+            self.coef_shape = (batch_size, sequence_length, self.jpeg_info.total_blocks, 64)
+            self.qtab_shape = (batch_size, sequence_length, self.jpeg_info.components, 64)
 
     def float_shape(self, k):
         fmt, dim, minus = self.float_keys[k]
@@ -157,6 +218,26 @@ class VideoPipeline(object):
         if rc != 0:
             raise RuntimeError('input pipeline: %s (%s, %d)' % (get().savp_pipeline_error(self._h).decode(), ERRORS.get(rc, 'error'), rc))
         return images, floats
+
+    def next_jpeg(self, coef=None, qtab=None, windows=None, floats=None):
+        """jpeg pipelines: (coef int16 [B,T,total_blocks,64], qtab uint16 [B,T,components,64], windows int32 [B,2] or None, [float
+        arrays]) or None at the end of the data.  The arrays may be caller-provided (e.g. views of pinned memory)."""
+        np = self._np
+        if not self.jpeg:
+            raise RuntimeError('next_jpeg() on a pipeline of raw frames: use next()')
+        coef = np.empty(self.coef_shape, np.int16) if coef is None else coef
+        qtab = np.empty(self.qtab_shape, np.uint16) if qtab is None else qtab
+        if windows is None and self.random_crop:
+            windows = np.zeros((self.shape[0], 2), np.int32)
+        if floats is None:
+            floats = [np.empty(self.float_shape(k), dtype=np.float32) for k in range(len(self.float_keys))]
+        fp = (c_vp * max(1, len(floats)))(*[f.ctypes.data for f in floats]) if floats else None
+        rc = get().savp_pipeline_next_jpeg(self._h, coef.ctypes.data, qtab.ctypes.data, windows.ctypes.data if self.random_crop else None, fp)
+        if rc == EOF_CODE:
+            return None
+        if rc != 0:
+            raise RuntimeError('input pipeline: %s (%s, %d)' % (get().savp_pipeline_error(self._h).decode(), ERRORS.get(rc, 'error'), rc))
+        return coef, qtab, (windows if self.random_crop else None), floats
 
     def close(self):
         if self._h:

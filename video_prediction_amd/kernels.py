@@ -1692,6 +1692,49 @@ def u8_frames_resize_f32(frames_u8, out_tm, crop):
               'savp_u8_frames_resize_f32')
 
 
+def jpeg_args(info, n_frames, out_hw=None):
+    """SavpJpegArgs for n_frames frames of the geometry `info` (io.SavpJpegInfo or a dict of its fields); pointers unset."""
+    get = (lambda k: info[k]) if isinstance(info, dict) else (lambda k: getattr(info, k))
+    a = lib.SavpJpegArgs()
+    a.N, a.width, a.height, a.components, a.total_blocks = int(n_frames), get('width'), get('height'), get('components'), get('total_blocks')
+    for k in ('h', 'v', 'blocks_w', 'blocks_h', 'block_offset'):
+        vals = list(get(k))
+        for c in range(a.components):
+            getattr(a, k)[c] = int(vals[c])
+    a.out_h, a.out_w = out_hw if out_hw is not None else (a.height, a.width)
+    return a
+
+
+def jpeg_workspace_bytes(info, n_frames):
+    n = int(_L().savp_jpeg_workspace_bytes(ctypes.byref(jpeg_args(info, n_frames))))
+    if n < 0:
+        raise ValueError('jpeg: unsupported or inconsistent geometry')
+    return n
+
+
+def jpeg_decode_u8(coef, qtab, info, out, ws, window=None):
+    """The device half of tf.image.decode_jpeg (include/savp_hip.h: savp_jpeg_decode_u8).  coef int16 [N, total_blocks, 64] and qtab
+    uint16 / int16 bits [N, components, 64] as the host entropy decoder delivers them (leading dimensions are flattened), info their
+    geometry; out uint8 [N, out_h, out_w, components]; ws a uint8 device tensor of jpeg_workspace_bytes(); window int32 [N, 2] of
+    (y0, x0) selects an out_h x out_w window per frame (without it out is the whole image).  Equals libjpeg-turbo's default decode."""
+    for t, dt in ((coef, (torch.int16,)), (qtab, (torch.int16, torch.uint16)), (out, (torch.uint8,)), (ws, (torch.uint8,))):
+        if not (t.is_cuda and t.dtype in dt and t.is_contiguous()):
+            raise RuntimeError('jpeg_decode_u8: contiguous device tensors (int16 coef, 16-bit qtab, uint8 out / ws) expected; there is no CPU path')
+    if out.dim() < 4:
+        raise ValueError('jpeg_decode_u8: out is [..., out_h, out_w, components]')
+    out_h, out_w, C = out.shape[-3:]
+    N = out.numel() // max(1, out_h * out_w * C)
+    a = jpeg_args(info, N, (out_h, out_w))
+    if C != a.components or coef.numel() != N * a.total_blocks * 64 or qtab.numel() != N * C * 64:
+        raise ValueError('jpeg_decode_u8: coef %r / qtab %r / out %r do not fit the geometry' % (tuple(coef.shape), tuple(qtab.shape), tuple(out.shape)))
+    if window is not None:
+        if not (window.is_cuda and window.dtype == torch.int32 and window.is_contiguous() and window.numel() == 2 * N):
+            raise ValueError('jpeg_decode_u8: window is a contiguous int32 device tensor [N, 2]')
+        a.window = window.data_ptr()
+    a.coef, a.qtab, a.out, a.ws, a.ws_bytes = coef.data_ptr(), qtab.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel()
+    lib.check(_L().savp_jpeg_decode_u8(lib.stream(), ctypes.byref(a)), 'savp_jpeg_decode_u8')
+
+
 class KernelTimer(object):
     """Kernel-only timing of single instrumented launches (bench.py): event pairs handed to the launcher through savp_prof_arm,
     stamped by the dispatch itself (the duration rocprofv3's kernel trace reports).  arm() before the launch, taken() after it

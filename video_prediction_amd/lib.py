@@ -41,6 +41,15 @@ class SavpConvArgs(ctypes.Structure):
     ]
 
 
+class SavpJpegArgs(ctypes.Structure):
+    _fields_ = [
+        ('N', c_i32), ('width', c_i32), ('height', c_i32), ('components', c_i32),
+        ('h', c_i32 * 3), ('v', c_i32 * 3), ('blocks_w', c_i32 * 3), ('blocks_h', c_i32 * 3), ('block_offset', c_i32 * 3),
+        ('total_blocks', c_i32), ('out_h', c_i32), ('out_w', c_i32),
+        ('coef', c_vp), ('qtab', c_vp), ('window', c_vp), ('out', c_vp), ('ws', c_vp), ('ws_bytes', c_i64),
+    ]
+
+
 _lib = None
 
 
@@ -145,6 +154,7 @@ def _declare(lib):
     _sig(lib, 'savp_tiled_z_grad', [c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i64])
     _sig(lib, 'savp_tiled_z_workspace_bytes', [c_i64, c_i32], restype=c_i64)
     _sig(lib, 'savp_eval_fold_ws_floats', [c_i32, c_i32, c_i32, c_i32], restype=c_i64)
+    _sig(lib, 'savp_jpeg_workspace_bytes', [P(SavpJpegArgs)], restype=c_i64)
     for name, argtypes in _EXTRA_SIGS.items():
         _sig(lib, name, argtypes)
 
@@ -316,6 +326,7 @@ register('savp_axpby', [c_vp, c_i64, c_f32, c_vp, c_f32, c_vp, c_vp])
 register('savp_fill_view', [c_vp, SavpView, c_i64, c_i32, c_i32, c_f32])
 register('savp_u8_frames_to_f32', [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64])
 register('savp_u8_frames_resize_f32', [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32])
+register('savp_jpeg_decode_u8', [c_vp, ctypes.POINTER(SavpJpegArgs)])
 register('savp_frame_mse_psnr', [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp])
 register('savp_frame_ssim', [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp])
 register('savp_eval_accumulate', [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32])
