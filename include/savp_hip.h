@@ -698,6 +698,54 @@ int savp_eval_fold_samples(void* stream, const float* target, int64_t t_st, int6
                            int32_t F, int32_t T1, int32_t S, int32_t B, int32_t H, int32_t W, int32_t C, const int32_t* n_valid,
                            const SavpEvalFoldState* states, float* ws, int64_t ws_floats);
 
+/* The same fold for ONE metric that the caller has already computed per frame (LPIPS): metric [F, S*B] contiguous, rows n = s*B + b, larger
+ * = better like the others.  state is updated for s = 0 .. *n_valid - 1 ascending with exactly the rule above (strict < / >, ties keep the
+ * earlier sample, fp32 sums in sample order, winners' whole sequences gathered from pred [T1, S*B, inner]).  sel: 2*B int32 of scratch.
+ * Two launches, no atomics. */
+int savp_eval_fold_metric(void* stream, const float* metric, const float* pred, int64_t p_st, int64_t p_sb, int32_t F, int32_t T1,
+                          int32_t S, int32_t B, int32_t inner, const int32_t* n_valid, const SavpEvalFoldState* state, int32_t* sel);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * LPIPS (lpips.hip): the learned perceptual distance of metrics.py:17-24 -- lpips_tf's defaults: AlexNet trunk, linear heads, v0.1.
+ * Everything fp32, stream-ordered, no allocation, every sum in a fixed order.  conv2..conv5 of the trunk are savp_conv FPROP calls
+ * (SAVP_PREC_F32, bias, SAVP_ACT_LRELU with alpha 0); the entries below are the parts savp_conv does not cover.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SAVP_LPIPS_TAPS 5
+#define SAVP_LPIPS_STEM_CO 64          /* conv1's output channels */
+#define SAVP_LPIPS_STEM_KROW 36        /* one kernel row of conv1 in the packed weights: 11 taps x 3 channels, zero-padded to 36 */
+/* conv1 of the trunk on frames in [0, 1]: frame (i0, i1) = x + i0 * x_s0 + i1 * x_s1 (elements), [H, W, C] contiguous, C = 1 (broadcast to
+ * three channels) or 3, i1 < N1, N frames in all.  On load v -> ((2 v - 1) - shift_c) / scale_c; taps outside the image contribute exactly
+ * 0.  Then 11x11 stride 4 pad 2 cross-correlation, + bias, ReLU -> y [N, Ho, Wo, 64] with Ho = (H + 4 - 11) / 4 + 1.  wp: the weights as
+ * [ky = 11][kp = 18][co = 64][2] with wp[ky][kp][co][e] = W_hwio[ky][kx][c][co] for kx * 3 + c = 2 kp + e (zero for 2 kp + e >= 33).
+ * One workgroup per (frame, strip of output rows): the input rows of the strip are staged in LDS once, the weights row by row, and the
+ * contraction runs on v_mfma_f32_32x32x2_f32.  SAVP_EINVAL when a strip does not fit 64 KB of LDS (W beyond ~400) or H, W < 7. */
+int savp_lpips_stem(void* stream, const float* x, int64_t x_s0, int64_t x_s1, int32_t N, int32_t N1, int32_t H, int32_t W, int32_t C,
+                    const float* wp, const float* bias, float* y);
+/* max-pool 3x3 stride 2, no padding, floor: x [N, H, W, C] -> y [N, (H - 3) / 2 + 1, (W - 3) / 2 + 1, C], both contiguous, C % 4 == 0 */
+int savp_lpips_maxpool3s2(void* stream, const float* x, int32_t N, int32_t H, int32_t W, int32_t C, float* y);
+/* The head: for output (f, n), f < F, n < N,
+ *     out[f * out_n1 + n] = sign * sum_l mean_p sum_c lin_l[c] * (a_l[p, c] / (|a_l[p, :]| + 1e-10) - b_l[p, c] / (|b_l[p, :]| + 1e-10))^2
+ * where a_l = a[l] + (f * a_n1 + n) * hw[l] * c[l] and b_l = b[l] + (f * b_n1 + n % b_mod) * hw[l] * c[l] are [hw[l], c[l]] tap maps
+ * (c[l] <= 384).  One workgroup per output, one wave per pixel, taps summed l = 0 .. 4 in order.  ctl (optional, DEVICE memory, int32[2]
+ * = {n_valid, base}): with s = s0 + n / B, the output is computed only when s < n_valid and, if nd > 0, 0 < base + s <= nd (the
+ * diversity pairs of base_model.py:194-198); the others are left untouched. */
+typedef struct {
+    int32_t F, N;
+    int32_t hw[SAVP_LPIPS_TAPS], c[SAVP_LPIPS_TAPS];
+    const float* a[SAVP_LPIPS_TAPS];
+    const float* b[SAVP_LPIPS_TAPS];
+    const float* lin[SAVP_LPIPS_TAPS];
+    int32_t a_n1, b_n1, b_mod, out_n1;
+    float sign;
+    float* out;
+    const int32_t* ctl;
+    int32_t B, s0, nd;
+} SavpLpipsHeadArgs;
+int savp_lpips_head(void* stream, const SavpLpipsHeadArgs* a);
+/* eval_diversity's running sum (base_model.py:194-198): div[f, b] += dv[f, s*B + b] for s = 0 .. n_valid-1 ascending with
+ * 0 < base + s <= nd; ctl = {n_valid, base} in DEVICE memory; dv [F, S*B], div [F, B] contiguous. */
+int savp_lpips_diversity_add(void* stream, const float* dv, int32_t F, int32_t S, int32_t B, const int32_t* ctl, int32_t nd, float* div);
+
 /* Fold float64 accumulators into fp32 gradients (round 6): dst[i] += (float) src[i] ; src[i] = 0 for i in idx[0 .. n) (idx NULL: i = 0 .. n-1).
  * The parameter gradients that many workgroups add to are accumulated in a float64 twin of the gradient arena (SavpInormArgs.dgamma, ...)
  * and rounded to fp32 once, here, before the optimiser (base_model.py:486-510) or the gradient exchange reads them.  Elements whose

@@ -8,8 +8,9 @@ save_prediction_eval_results (:77-113): per subtask (max / avg / min) and metric
 `metrics/<metric>.csv`, which the reference's combine_results.py / plot_results.py read; then the closing psnr / ssim table (:266-285).
 
 The samples are drawn by SAVPVideoPredictionModel.eval_outputs_and_metrics_fn with the model's eval_parallel_iterations: S prior
-samples per generator unroll, folded on the GPU (SAVPEngine.eval_outputs_and_metrics).  psnr, ssim and mse are produced; lpips and
-eval_diversity need external AlexNet weights and are not.
+samples per generator unroll, folded on the GPU (SAVPEngine.eval_outputs_and_metrics).  psnr, ssim and mse are always produced; lpips and
+eval_diversity need the AlexNet / LPIPS weights, which the user brings: a file written by scripts/convert_lpips_weights.py, named by the
+SAVP_LPIPS_WEIGHTS environment variable (video_prediction_amd/lpips.py).  Without it they are not computed and a line says so.
 """
 from __future__ import absolute_import, division, print_function
 
@@ -58,7 +59,7 @@ _FLAGS = (
     ('synthetic_shape', dict(type=str, default='64,64,3', help="H,W,C of --dataset synthetic (not in the reference)")),
 )
 
-UNAVAILABLE_METRICS = ('lpips', 'eval_diversity')
+UNAVAILABLE_METRICS = ('lpips', 'eval_diversity')      # without LPIPS weights (SAVP_LPIPS_WEIGHTS unset)
 
 
 def build_parser():
@@ -231,7 +232,8 @@ def main(argv=None):
             f.write(json.dumps(content, sort_keys=True, indent=4))
     if args.checkpoint:
         model.restore(args.checkpoint)
-    print('%s are not computed: they need external AlexNet weights' % ' and '.join(UNAVAILABLE_METRICS))
+    if model.engine.lpips is None:
+        print('%s are not computed: they need external AlexNet weights' % ' and '.join(UNAVAILABLE_METRICS))
 
     sample_ind = 0
     while inputs is not None and not (args.num_samples and sample_ind >= args.num_samples):

@@ -316,3 +316,65 @@ extern "C" int savp_eval_fold_samples(void* stream, const float* target, int64_t
                        (int)inner, n_valid, st, (const int*)sel);
     return LAUNCH_OK();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// savp_eval_fold_metric: fold_select_kernel's phase 2 and fold_gather_kernel for ONE metric the caller computed per frame (LPIPS).
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// single workgroup, one thread per b: eval_accumulate_kernel's update for s = 0 .. n_valid-1 in order; sel[0 | 1][b] = the last sample that
+// replaced the running min / max (-1: none)
+__global__ __launch_bounds__(NT) void fold_metric_select_kernel(const float* metric, int F, int SB, int B, const int* n_valid,
+                                                                SavpEvalFoldState st, int* sel) {
+    const int nv = *n_valid;
+    for (int b = threadIdx.x; b < B; b += NT) {
+        int smin_i = -1, smax_i = -1;
+        for (int s = 0; s < nv; ++s) {
+            const int n = s * B + b;
+            float sm = 0.f, smin = 0.f, smax = 0.f;
+            for (int t = 0; t < F; ++t) { sm += metric[t * SB + n]; smin += st.vmin[t * B + b]; smax += st.vmax[t * B + b]; }
+            const bool lo = sm / (float)F < smin / (float)F, hi = sm / (float)F > smax / (float)F;
+            for (int t = 0; t < F; ++t) {
+                const float m = metric[t * SB + n];
+                if (lo) st.vmin[t * B + b] = m;
+                if (hi) st.vmax[t * B + b] = m;
+                st.vsum[t * B + b] += m;
+            }
+            if (lo) smin_i = s;
+            if (hi) smax_i = s;
+        }
+        sel[b] = smin_i;
+        sel[B + b] = smax_i;
+    }
+}
+
+// grid (x: slices of the frame, y: t, z: b), as fold_gather_kernel
+__global__ __launch_bounds__(NT) void fold_metric_gather_kernel(const float* pred, long long p_st, long long p_sb, int B, int inner,
+                                                                const int* n_valid, SavpEvalFoldState st, const int* sel) {
+    const int t = blockIdx.y, b = blockIdx.z;
+    const int nv = *n_valid;
+    const size_t o = ((size_t)t * B + b) * inner;
+    const float* px = pred + t * p_st + b * p_sb;
+    const int smin = sel[b], smax = sel[B + b];
+    for (int i = blockIdx.x * NT + threadIdx.x; i < inner; i += gridDim.x * NT) {
+        float acc = st.gsum[o + i];
+        for (int s = 0; s < nv; ++s) acc = acc + px[(long long)s * B * p_sb + i];
+        st.gsum[o + i] = acc;
+        if (smin >= 0) st.gmin[o + i] = px[(long long)smin * B * p_sb + i];
+        if (smax >= 0) st.gmax[o + i] = px[(long long)smax * B * p_sb + i];
+    }
+}
+
+extern "C" int savp_eval_fold_metric(void* stream, const float* metric, const float* pred, int64_t p_st, int64_t p_sb, int32_t F, int32_t T1,
+                                     int32_t S, int32_t B, int32_t inner, const int32_t* n_valid, const SavpEvalFoldState* state,
+                                     int32_t* sel) {
+    if (!metric || !pred || !n_valid || !state || !sel || F < 1 || T1 < F || S < 1 || B < 1 || inner < 1) return SAVP_EINVAL;
+    const SavpEvalFoldState st = *state;
+    if (!st.vmin || !st.vsum || !st.vmax || !st.gmin || !st.gsum || !st.gmax) return SAVP_EINVAL;
+    if ((int64_t)F * S * B > 0x7fffffff) return SAVP_EINVAL;
+    hipStream_t sm = (hipStream_t)stream;
+    hipLaunchKernelGGL(fold_metric_select_kernel, dim3(1), dim3(NT), 0, sm, metric, F, S * B, B, n_valid, st, sel);
+    unsigned gx = (unsigned)((inner + NT * 4 - 1) / (NT * 4));
+    if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(fold_metric_gather_kernel, dim3(gx, (unsigned)T1, (unsigned)B), dim3(NT), 0, sm, pred, (long long)p_st,
+                       (long long)p_sb, B, inner, n_valid, st, (const int*)sel);
+    return LAUNCH_OK();
+}

@@ -1665,6 +1665,85 @@ def eval_fold_samples(target, pred, n_valid, states, ws):
                                           arr, _p(ws), ws.numel()), 'savp_eval_fold_samples')
 
 
+def eval_fold_metric(metric, pred, n_valid, state, sel):
+    """eval_fold_samples' fold for one precomputed metric [F, S*B] (larger = better): state = dict(min, sum, max: [F, B], gmin, gsum, gmax:
+    [T1, B, ...]) updated in place for the first n_valid samples of pred [T1, S*B, ...]; sel: int32 [2 * B] scratch."""
+    lib.require_device(metric, pred)
+    _require_i32(n_valid, sel)
+    F, SB = metric.shape
+    T1 = pred.shape[0]
+    B = state['min'].shape[1]
+    p_st, p_sb, inner = _tb(pred)
+    if pred.shape[1] != SB or SB % B or T1 < F or not metric.is_contiguous() or sel.numel() < 2 * B:
+        raise ValueError('eval_fold_metric: metric %r does not fit pred %r' % (tuple(metric.shape), tuple(pred.shape)))
+    for key, shape in (('min', (F, B)), ('sum', (F, B)), ('max', (F, B)), ('gmin', (T1, B)), ('gsum', (T1, B)), ('gmax', (T1, B))):
+        v = state[key]
+        lib.require_device(v)
+        if tuple(v.shape[:2]) != shape or not v.is_contiguous() or v[0, 0].numel() != (1 if len(key) == 3 else inner):
+            raise ValueError('eval_fold_metric: state %s must be contiguous fp32 %r + frame' % (key, shape))
+    st = lib.SavpEvalFoldState(_p(state['min']), _p(state['sum']), _p(state['max']), _p(state['gmin']), _p(state['gsum']), _p(state['gmax']))
+    lib.check(_L().savp_eval_fold_metric(lib.stream(), _p(metric), _p(pred), p_st, p_sb, F, T1, SB // B, B, inner, _p(n_valid),
+                                         ctypes.byref(st), _p(sel)), 'savp_eval_fold_metric')
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# LPIPS (csrc/lpips.hip); the launch sequence lives in video_prediction_amd/lpips.py
+# ---------------------------------------------------------------------------------------------------------------
+def lpips_stem(frames, wp, bias, y):
+    """frames [N0, N1, H, W, C] (C = 1 | 3, contiguous frames, any leading strides) in [0, 1] -> y [N0*N1, Ho, Wo, 64] contiguous: input
+    affine + conv1 + bias + ReLU.  wp: the weights packed as include/savp_hip.h describes (lpips.pack_stem_weights)."""
+    lib.require_device(frames, wp, bias, y)
+    s0, s1, _ = _tb(frames)
+    N0, N1, H, W, C = frames.shape
+    Ho, Wo = (H + 4 - 11) // 4 + 1, (W + 4 - 11) // 4 + 1
+    if tuple(y.shape) != (N0 * N1, Ho, Wo, 64) or not y.is_contiguous() or wp.numel() != 11 * lib.LPIPS_STEM_KROW * 64 or bias.numel() != 64:
+        raise ValueError('lpips_stem: y %r / weights do not fit frames %r' % (tuple(y.shape), tuple(frames.shape)))
+    lib.check(_L().savp_lpips_stem(lib.stream(), _p(frames), s0, s1, N0 * N1, N1, H, W, C, _p(wp), _p(bias), _p(y)), 'savp_lpips_stem')
+
+
+def lpips_maxpool3s2(x, y):
+    """x [N, H, W, C] -> y [N, (H-3)//2+1, (W-3)//2+1, C], contiguous."""
+    lib.require_device(x, y)
+    N, H, W, C = x.shape
+    if tuple(y.shape) != (N, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C) or not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError('lpips_maxpool3s2: y %r does not fit x %r' % (tuple(y.shape), tuple(x.shape)))
+    lib.check(_L().savp_lpips_maxpool3s2(lib.stream(), _p(x), N, H, W, C, _p(y)), 'savp_lpips_maxpool3s2')
+
+
+def lpips_head(taps_a, taps_b, lins, out, sign, F, N, a_n1, b_n1, b_mod, out_n1, a_off=0, b_off=0, out_off=0, ctl=None, B=1, s0=0, nd=0):
+    """include/savp_hip.h savp_lpips_head.  taps_*: five contiguous [frames, h, w, c] tensors; *_off: frame (out: element) offsets applied to
+    the base pointers; ctl: int32 [2] device tensor {n_valid, base} or None."""
+    lib.require_device(out, *(list(taps_a) + list(taps_b) + list(lins)))
+    _require_i32(ctl)
+    a = lib.SavpLpipsHeadArgs()
+    a.F, a.N, a.a_n1, a.b_n1, a.b_mod, a.out_n1, a.sign = int(F), int(N), int(a_n1), int(b_n1), int(b_mod), int(out_n1), float(sign)
+    for l in range(lib.LPIPS_TAPS):
+        ta, tb = taps_a[l], taps_b[l]
+        if tuple(ta.shape[1:]) != tuple(tb.shape[1:]) or not (ta.is_contiguous() and tb.is_contiguous()) or lins[l].numel() != ta.shape[-1]:
+            raise ValueError('lpips_head: tap %d: %r against %r' % (l, tuple(ta.shape), tuple(tb.shape)))
+        fs = ta[0].numel()
+        if (F - 1) * a_n1 + N + a_off > ta.shape[0] or (F - 1) * b_n1 + min(N, b_mod) + b_off > tb.shape[0]:
+            raise ValueError('lpips_head: tap %d has too few frames' % l)
+        a.hw[l], a.c[l] = ta.shape[1] * ta.shape[2], ta.shape[3]
+        a.a[l], a.b[l], a.lin[l] = ta.data_ptr() + 4 * a_off * fs, tb.data_ptr() + 4 * b_off * fs, lins[l].data_ptr()
+    if (F - 1) * out_n1 + N + out_off > out.numel() or not out.is_contiguous():
+        raise ValueError('lpips_head: out is too small')
+    a.out = out.data_ptr() + 4 * out_off
+    a.ctl, a.B, a.s0, a.nd = _p(ctl), int(B), int(s0), int(nd)
+    lib.check(_L().savp_lpips_head(lib.stream(), ctypes.byref(a)), 'savp_lpips_head')
+
+
+def lpips_diversity_add(dv, ctl, nd, div):
+    """div [F, B] += dv [F, S*B] over the samples s < ctl[0] with 0 < ctl[1] + s <= nd, ascending."""
+    lib.require_device(dv, div)
+    _require_i32(ctl)
+    F, B = div.shape
+    if dv.shape[0] != F or dv.shape[1] % B or not (dv.is_contiguous() and div.is_contiguous()):
+        raise ValueError('lpips_diversity_add: dv %r does not fit div %r' % (tuple(dv.shape), tuple(div.shape)))
+    lib.check(_L().savp_lpips_diversity_add(lib.stream(), _p(dv), F, dv.shape[1] // B, B, _p(ctl), int(nd), _p(div)),
+              'savp_lpips_diversity_add')
+
+
 def u8_frames_to_f32(frames_u8, out_tm):
     """uint8 [B, T, H, W, C] -> float32 time-major [T, B, H, W, C] / 255 (base_dataset.py:187 + transpose_batch_time)."""
     if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()):

@@ -342,6 +342,24 @@ class SavpEvalFoldState(ctypes.Structure):
 
 register('savp_eval_fold_samples', [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
                                     ctypes.POINTER(SavpEvalFoldState), c_vp, c_i64])
+register('savp_eval_fold_metric', [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                   ctypes.POINTER(SavpEvalFoldState), c_vp])
+
+LPIPS_TAPS = 5                    # SAVP_LPIPS_TAPS
+LPIPS_STEM_KROW = 36              # SAVP_LPIPS_STEM_KROW
+
+
+class SavpLpipsHeadArgs(ctypes.Structure):
+    _fields_ = [('F', c_i32), ('N', c_i32), ('hw', c_i32 * LPIPS_TAPS), ('c', c_i32 * LPIPS_TAPS),
+                ('a', c_vp * LPIPS_TAPS), ('b', c_vp * LPIPS_TAPS), ('lin', c_vp * LPIPS_TAPS),
+                ('a_n1', c_i32), ('b_n1', c_i32), ('b_mod', c_i32), ('out_n1', c_i32), ('sign', c_f32),
+                ('out', c_vp), ('ctl', c_vp), ('B', c_i32), ('s0', c_i32), ('nd', c_i32)]
+
+
+register('savp_lpips_stem', [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp])
+register('savp_lpips_maxpool3s2', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp])
+register('savp_lpips_head', [c_vp, ctypes.POINTER(SavpLpipsHeadArgs)])
+register('savp_lpips_diversity_add', [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp])
 register('savp_adam', [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp])
 register('savp_cdna_kernels_fwd', [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])
 register('savp_cdna_kernels_bwd', [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])

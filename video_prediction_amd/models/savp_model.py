@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import kernels as K
+from .. import lpips as _lpips
 from .. import variables as V
 from ..engine import ParamStore, copy_view, add_views
 from .base_model import VideoPredictionModel, learning_rate, kl_weight
@@ -126,9 +127,11 @@ class SAVPEngine(object):
     UNSUPPORTED_WEIGHTS = ('vgg_cdist_weight', 'feature_l2_weight', 'ae_l2_weight')
 
     def __init__(self, hp, image_shape, batch_size, mode='train', values=None, seed=4, device='cuda:0', base_seed=0, rank=0,
-                 cond=(0, 0)):
+                 cond=(0, 0), lpips_weights=None):
         """cond = (n_actions, n_states): the widths of inputs['actions'] [B, T-1, na] / inputs['states'] [B, T, ns] when the dataset
-        supplies them (the action / state-conditioned model, savp_model.py:24-26,411-444,655-661; base_model.py:758-762)."""
+        supplies them (the action / state-conditioned model, savp_model.py:24-26,411-444,655-661; base_model.py:758-762).
+        lpips_weights: path of the LPIPS network's .npz (video_prediction_amd.lpips; default: the SAVP_LPIPS_WEIGHTS environment
+        variable); without one the lpips metric and eval_diversity are not produced."""
         self.hp, self.mode, self.B = hp, mode, batch_size
         bad = [k for k in self.UNSUPPORTED_WEIGHTS if getattr(hp, k, 0)]
         if bad and mode == 'train':
@@ -227,6 +230,11 @@ class SAVPEngine(object):
         self.eager_steps = 0
         self.infer_graph = os.environ.get('SAVP_INFER_GRAPH', '1') == '1' and self.device.type == 'cuda'
         self.gen_graph, self.gen_graph_out, self.gen_eager = None, None, 0
+        self.lpips, self._lp = None, None
+        path = _lpips.configured_path(lpips_weights)
+        if path:
+            self.lpips = _lpips.Lpips(_lpips.load_weights(path), self.device)
+            self.METRICS = SAVPEngine.METRICS + ('lpips',)         # base_model.py:119-124, all four
 
     # -- data-parallel replicas (base_model.py:517-692 / tf_utils.allreduce_grads) ---------------------------------
     def attach_process_group(self, dist_module, force=None):
@@ -743,20 +751,41 @@ class SAVPEngine(object):
         return body()
 
     # -- evaluation: metrics_fn / eval_outputs_and_metrics_fn (base_model.py:113-227) ------------------------
-    METRICS = ('psnr', 'mse', 'ssim')            # base_model.py:119-124 without lpips (external AlexNet weights)
+    METRICS = ('psnr', 'mse', 'ssim')            # base_model.py:119-124; + 'lpips' on an instance with LPIPS weights (__init__)
 
-    def _frame_metrics(self, pred, buf):
-        """psnr / mse / ssim [T_future, B] of the future frames of pred [T1, B, H, W, C] against the staged images."""
+    def _lpips_sets(self):
+        """Feature sets of the future frames of one [.., B, ..] unroll: the target's, the current sample's, the previous sample's."""
+        if self._lp is None:
+            fut = self.T - self.hp.context_frames
+            H, W, _ = self.image_shape
+            self._lp = {k: self.lpips.feature_set(fut * self.B, H, W) for k in ('tgt', 'cur', 'prev')}
+        return self._lp
+
+    def _lpips_target(self):
+        """The trunk on the future frames of the staged images: once per staged batch, whatever the number of samples."""
+        lp = self._lpips_sets()
+        self.lpips.features(self.images_tm[self.hp.context_frames:], lp['tgt'])
+        return lp['tgt']
+
+    def _frame_metrics(self, pred, buf, target_ready=False):
+        """psnr / mse / ssim (/ lpips: minus the distance, metrics.py:17-24) [T_future, B] of the future frames of pred [T1, B, H, W, C]
+        against the staged images.  target_ready: _lpips_target() already ran for this batch."""
         hp = self.hp
         fut = self.T - hp.context_frames
         target = self.images_tm[self.T - fut:]
         p = pred[self.T1 - fut:]
         K.frame_mse_psnr(target, p, mse=buf['mse'], psnr=buf['psnr'])
         K.frame_ssim(target, p, buf['ssim'])
+        if self.lpips is not None:
+            lp = self._lpips_sets()
+            if not target_ready:
+                self._lpips_target()
+            self.lpips.features(p, lp['cur'])
+            self.lpips.distance(lp['cur'], lp['tgt'], buf['lpips'], sign=-1.0)
         return buf
 
     def metrics(self, gen=None):
-        """metrics_fn (base_model.py:113-130): mean psnr / mse / ssim over the future frames of the prior unroll."""
+        """metrics_fn (base_model.py:113-130): mean psnr / mse / ssim (/ lpips) over the future frames of the prior unroll."""
         gen = self.generate() if gen is None else gen
         fut = self.T - self.hp.context_frames
         buf = {k: torch.empty(fut, self.B, device=self.device) for k in self.METRICS}
@@ -769,21 +798,23 @@ class SAVPEngine(object):
             return noises[s_i]
         return self.default_noise(torch.Generator().manual_seed(self._noise_seed(self.step, stream=1 + s_i)))
 
-    def eval_outputs_and_metrics(self, num_samples=100, noises=None, parallel_iterations=1):
+    def eval_outputs_and_metrics(self, num_samples=100, noises=None, parallel_iterations=1, num_samples_for_diversity=10):
         """eval_outputs_and_metrics_fn (base_model.py:132-227): draw num_samples prior unrolls; per metric keep, for every
         sequence, the sample whose time-mean is smallest / largest, and the running mean.  noises: optional list of noise dicts
         (one per sample; default = fresh draws).  Returns (eval_outputs, eval_metrics) with the reference's keys, time-major;
-        the lpips / eval_diversity entries need external network weights and are not produced.
+        the lpips / eval_diversity entries (:194-198,211,226: the mean LPIPS distance between the future frames of samples i and i-1 for
+        0 < i <= num_samples_for_diversity) are produced when LPIPS weights are configured (video_prediction_amd.lpips).
         parallel_iterations = S > 1 (the reference's tf.foldl(parallel_iterations=S), base_model.py:199-201): S prior samples per
         unroll of a generator of batch S*B, folded by one fused kernel (_ParallelPriorEval); sample i sees the same draws as here."""
         S = int(parallel_iterations or 1)
         if S < 1:
             raise ValueError('parallel_iterations must be >= 1, got %r' % (parallel_iterations,))
         if S > 1 and self.nz:
-            key = (S, K.PRECISION['value'])
+            nd = int(num_samples_for_diversity) if self.lpips is not None else 0
+            key = (S, K.PRECISION['value']) + ((nd,) if self.lpips is not None else ())       # nd is part of the captured sequence
             ev = getattr(self, '_par_eval', {}).get(key)
             if ev is None:
-                self._par_eval = {key: _ParallelPriorEval(self, S)}      # one sampler at a time: it holds an S*B generator
+                self._par_eval = {key: _ParallelPriorEval(self, S, nd)}  # one sampler at a time: it holds an S*B generator
                 ev = self._par_eval[key]
             return ev.run(num_samples, noises)
         hp, B, dev = self.hp, self.B, self.device
@@ -807,11 +838,21 @@ class SAVPEngine(object):
                          gsum=torch.zeros(shape, device=dev), gmax=torch.zeros(shape, device=dev))
         cmin = torch.zeros(B, dtype=torch.int32, device=dev)
         cmax = torch.zeros(B, dtype=torch.int32, device=dev)
+        nd = int(num_samples_for_diversity)
+        if self.lpips is not None:
+            self._lpips_target()
+            lp = self._lpips_sets()
+            div, dv = torch.zeros(fut, B, device=dev), torch.empty(fut, B, device=dev)
         for s_i in range(num_samples):                                 # accum_gen_images_and_metrics_fn (:176-198)
             gen = self.generate(noises[s_i] if noises else self.default_noise(
                 torch.Generator().manual_seed(self._noise_seed(self.step, stream=1 + s_i))))
             prior = gen[:, B:]                                         # the prior unroll ('gen_images')
-            self._frame_metrics(prior, buf)
+            self._frame_metrics(prior, buf, target_ready=True)
+            if self.lpips is not None:
+                if 0 < s_i <= nd:                                      # (:194-198): + the distance to the previous sample
+                    self.lpips.distance(lp['cur'], lp['prev'], dv, sign=1.0)
+                    K.axpby(1.0, dv.reshape(-1), 1.0, div.reshape(-1), div.reshape(-1))
+                lp['cur'], lp['prev'] = lp['prev'], lp['cur']          # this sample's taps are the next one's `prev`: no second forward
             for k in self.METRICS:
                 a = st[k]
                 K.eval_accumulate(buf[k], a['min'], a['sum'], a['max'], cmin, cmax)
@@ -829,7 +870,15 @@ class SAVPEngine(object):
             mets['eval_%s/min' % k] = a['min']
             mets['eval_%s/avg' % k] = a['sum']
             mets['eval_%s/max' % k] = a['max']
+        if self.lpips is not None:                                     # (:226): the divisor is nd even when fewer pairs were added
+            mets['eval_diversity'] = div / float(nd) if nd else torch.zeros_like(div)
         return outs, mets
+
+
+def chunk_controls(num_samples, S):
+    """[(valid samples, index of the first sample)] of the chunks of S samples that cover num_samples: what _ParallelPriorEval puts into
+    device memory in front of every replay of its one launch sequence.  Only the last chunk can be short."""
+    return [(min(S, num_samples - base), base) for base in range(0, num_samples, S)]
 
 
 class _ParallelPriorEval(object):
@@ -841,9 +890,15 @@ class _ParallelPriorEval(object):
     chunk of S samples: one device-to-device copy stages the chunk's draws and its count of valid samples, then ONE launch sequence --
     z = mu + sigma * eps per sample (the same reparam_fwd launch the sequential path runs, so the same bits), the prior unroll and the fused
     metric + fold kernel (kernels.eval_fold_samples) -- runs eagerly the first time and as one captured hipGraph afterwards.  A last chunk
-    with fewer than S samples is padded with zero draws that the fold never reads, so every chunk of a batch shape replays the same graph."""
+    with fewer than S samples is padded with zero draws that the fold never reads, so every chunk of a batch shape replays the same graph.
 
-    def __init__(self, eng, S):
+    With LPIPS weights configured the chunk's launch sequence also holds the trunk on the chunk's S*B future sequences, the head against the
+    target's taps (computed once per batch), the fold of that metric (kernels.eval_fold_metric) and the diversity pairs (i, i-1) for
+    0 < i <= nd: pairs inside the chunk from the chunk's own taps, the pair across the chunk boundary against the taps of the previous chunk's
+    last sample, which the sequence copies aside at its end.  The chunk's first sample index lies next to n_valid in device memory (self.ctl),
+    because every chunk replays the same graph."""
+
+    def __init__(self, eng, S, nd=0):
         hp, B, dev = eng.hp, eng.B, eng.device
         H, W, C = eng.image_shape
         self.eng, self.S, self.B = eng, S, B
@@ -864,7 +919,8 @@ class _ParallelPriorEval(object):
         self.n_eps = 0 if eng.learn_prior else S * T1 * B * nz
         self.n_second = S * T1 * B * nz if eng.learn_prior else F * N * nz
         self.stage = torch.zeros(self.n_eps + self.n_second, device=dev)
-        self.n_valid = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ctl = torch.zeros(2, dtype=torch.int32, device=dev)       # {valid samples of the chunk, index of its first sample}
+        self.n_valid = self.ctl[:1]
         self.zero_eps = torch.zeros(T1, B, nz, device=dev)
         self.z_tmp = torch.empty(T1, B, nz, device=dev)
         self.ls_tmp = torch.empty(T1, B, nz, device=dev)
@@ -872,7 +928,13 @@ class _ParallelPriorEval(object):
         shape = (T1, B, H, W, C)
         self.st = {k: dict(min=torch.empty(F, B, device=dev), sum=torch.empty(F, B, device=dev), max=torch.empty(F, B, device=dev),
                            gmin=torch.empty(shape, device=dev), gsum=torch.empty(shape, device=dev), gmax=torch.empty(shape, device=dev))
-                   for k in K.EVAL_FOLD_KEYS}
+                   for k in eng.METRICS}
+        self.nd = int(nd)
+        if eng.lpips is not None:
+            self.lp_cur, self.lp_prev = eng.lpips.feature_set(F * N, H, W), eng.lpips.feature_set(F * B, H, W)
+            self.lp_met, self.lp_dv = torch.empty(F, N, device=dev), torch.empty(F, N, device=dev)
+            self.lp_sel = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+            self.div = torch.zeros(F, B, device=dev)
         self.graph, self.eager = None, 0
         self.use_graph = eng.infer_graph
 
@@ -899,6 +961,9 @@ class _ParallelPriorEval(object):
             a['max'].fill_(float('-inf'))
             for k in ('sum', 'gmin', 'gsum', 'gmax'):
                 a[k].zero_()
+        if eng.lpips is not None:
+            eng._lpips_target()
+            self.div.zero_()
 
     def _host_draws(self, num_samples, noises):
         """All draws of the batch, chunk by chunk: float32 [chunks, stage size] and int32 [chunks] valid-sample counts."""
@@ -937,7 +1002,27 @@ class _ParallelPriorEval(object):
             copy_view(self.stage[self.n_eps:].view(self.F, self.N, nz), [self.zs[c1:]])
         gen = self.gen.forward(self.images, self.zs, self.gt, actions=self.actions, states=self.states)
         K.eval_fold_samples(eng.images_tm[eng.T - self.F:], gen, self.n_valid, self.st, self.ws)
+        if eng.lpips is not None:
+            self._chunk_lpips(gen)
         return gen
+
+    def _chunk_lpips(self, gen):
+        """lpips of the chunk's samples and its fold; the chunk's diversity pairs (rows n = s*B + b; gated on the device by self.ctl)."""
+        eng, S, B, F, N, nd = self.eng, self.S, self.B, self.F, self.N, self.nd
+        lp, cur, prev, tgt = eng.lpips, self.lp_cur, self.lp_prev, eng._lpips_sets()['tgt']
+        lp.features(gen[eng.T1 - F:], cur)
+        lp.head(cur, tgt, self.lp_met, -1.0, F=F, N=N, a_n1=N, b_n1=B, b_mod=B, out_n1=N, ctl=self.ctl, B=B)
+        K.eval_fold_metric(self.lp_met, gen, self.n_valid, self.st['lpips'], self.lp_sel)
+        if nd < 1:
+            return
+        if S > 1:                                      # samples 1 .. S-1 against their predecessor in this chunk
+            lp.head(cur, cur, self.lp_dv, 1.0, F=F, N=N - B, a_n1=N, b_n1=N, b_mod=N, out_n1=N, a_off=B, out_off=B, ctl=self.ctl, B=B,
+                    s0=1, nd=nd)
+        lp.head(cur, prev, self.lp_dv, 1.0, F=F, N=B, a_n1=N, b_n1=B, b_mod=B, out_n1=N, ctl=self.ctl, B=B, nd=nd)
+        K.lpips_diversity_add(self.lp_dv, self.ctl, nd, self.div)
+        for a, b in zip(cur.taps, prev.taps):          # the last sample's taps (only a last chunk is short, and nothing follows it)
+            hw, c = a.shape[1] * a.shape[2], a.shape[3]
+            copy_view(a.view(F, N, hw, c)[:, N - B:].reshape(F, B * hw, c), [b.view(F, B * hw, c)])
 
     def _run_chunk(self):
         if not (self.use_graph and K.fused_ok()):
@@ -963,16 +1048,17 @@ class _ParallelPriorEval(object):
             raise ValueError('num_samples must be >= 1')
         eng, dev = self.eng, self.eng.device
         self._stage_batch()
-        flat, nv = self._host_draws(num_samples, noises)
-        flat, nv = flat.to(dev), nv.to(dev)
+        flat, _ = self._host_draws(num_samples, noises)
+        ctl = torch.tensor(chunk_controls(num_samples, self.S), dtype=torch.int32)
+        flat, ctl = flat.to(dev), ctl.to(dev)
         for c in range(flat.shape[0]):
             self.stage.copy_(flat[c])
-            self.n_valid.copy_(nv[c:c + 1])
+            self.ctl.copy_(ctl[c])
             self._run_chunk()
         outs, mets = OrderedDict(), OrderedDict()
         outs['eval_images'] = eng.images_tm
         inv = 1.0 / float(num_samples)
-        for k in SAVPEngine.METRICS:                  # (:215-221); fresh tensors, as the sequential path returns
+        for k in eng.METRICS:                         # (:215-221); fresh tensors, as the sequential path returns
             a = {n: v.clone() for n, v in self.st[k].items()}
             K.axpby(inv, a['gsum'].reshape(-1), 0.0, a['gsum'].reshape(-1), a['gsum'].reshape(-1))
             K.axpby(inv, a['sum'].reshape(-1), 0.0, a['sum'].reshape(-1), a['sum'].reshape(-1))
@@ -982,6 +1068,8 @@ class _ParallelPriorEval(object):
             mets['eval_%s/min' % k] = a['min']
             mets['eval_%s/avg' % k] = a['sum']
             mets['eval_%s/max' % k] = a['max']
+        if eng.lpips is not None:                     # (:226)
+            mets['eval_diversity'] = self.div / float(self.nd) if self.nd else torch.zeros_like(self.div)
         return outs, mets
 
 
@@ -1140,6 +1228,8 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
     """savp_model.py:771-855."""
 
     def __init__(self, *args, **kwargs):
+        # path of the LPIPS network's weights (video_prediction_amd.lpips); None: the SAVP_LPIPS_WEIGHTS environment variable, if set
+        self.lpips_weights = kwargs.pop('lpips_weights', None)
         super(SAVPVideoPredictionModel, self).__init__(generator_fn, discriminator_fn, *args, **kwargs)
         if self.mode != 'train':
             self.discriminator_fn = None
@@ -1164,7 +1254,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         images = inputs['images']
         B = images.shape[0]
         self.engine = SAVPEngine(self.hparams, tuple(images.shape[2:]), B, mode=self.mode, values=values, seed=seed,
-                                 device=device, cond=cond_of(inputs))
+                                 device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights)
         self.saveable_variables = self.engine.store.names()
         self.post_init_ops = []
         self.outputs = {}
@@ -1199,7 +1289,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         return self.outputs
 
     def metrics_fn(self, inputs=None, outputs=None):
-        """base_model.py:113-130 on the current inputs (psnr / mse / ssim; lpips needs external weights)."""
+        """base_model.py:113-130 on the current inputs (psnr / mse / ssim, and lpips when its weights are configured)."""
         if inputs is not None:
             self.inputs = inputs
             self.engine.set_images(self.inputs)
@@ -1213,7 +1303,9 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
             self.inputs = inputs
             self.engine.set_images(self.inputs)
         self.eval_outputs, self.eval_metrics = self.engine.eval_outputs_and_metrics(
-            num_samples or self.eval_num_samples, noises, parallel_iterations=parallel_iterations or self.eval_parallel_iterations)
+            num_samples or self.eval_num_samples, noises, parallel_iterations=parallel_iterations or self.eval_parallel_iterations,
+            num_samples_for_diversity=(self.eval_num_samples_for_diversity if num_samples_for_diversity is None
+                                       else num_samples_for_diversity))
         return self.eval_outputs, self.eval_metrics
 
     def restore(self, checkpoints, restore_to_checkpoint_mapping=None):
