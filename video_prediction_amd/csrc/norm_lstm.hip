@@ -14,6 +14,7 @@
 #include "zero_fill.h"
 extern thread_local hipEvent_t g_savp_prof_start, g_savp_prof_stop;      // common.hip: savp_prof_arm
 #include "opts.h"
+#include "inorm_stream.h"
 
 #define NT 256
 
@@ -409,6 +410,18 @@ static int inorm_chunk(const SavpInormArgs* a) {
     return (int)c;
 }
 
+// option "inorm_fast": the apply pass by a shape-specialised kernel (inorm_stream.h) where one covers the call; 0 = the caller launches the generic one
+static int inorm_fast_fwd_ok(hipStream_t st, const SavpInormArgs* a, int chunk, int unshifted) {
+    if (!savp_opt(OPT_INORM_FAST) || !inorm_fast_fwd(st, a, chunk, unshifted)) return 0;
+    savp_opt_count(OPT_INORM_FAST_TAKEN);
+    return 1;
+}
+static int inorm_fast_bwd_ok(hipStream_t st, const SavpInormArgs* a, int chunk) {
+    if (savp_opt(OPT_INORM_FAST) != 1 || !inorm_fast_bwd(st, a, chunk)) return 0;      // 2: the forward pass alone (developer A/B)
+    savp_opt_count(OPT_INORM_FAST_TAKEN);
+    return 1;
+}
+
 extern "C" int savp_instnorm_act_fwd(void* stream, const SavpInormArgs* a) {
     if (!a || a->C % 4 || a->nout < 1 || a->nout > 4) return SAVP_EINVAL;
     InormP p;
@@ -428,7 +441,7 @@ extern "C" int savp_instnorm_act_fwd(void* stream, const SavpInormArgs* a) {
         hipStream_t st = (hipStream_t)stream;
         p.chunk = inorm_chunk(a);
         dim3 grid((a->HW + p.chunk - 1) / p.chunk, a->N);
-        hipLaunchKernelGGL(inorm_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws, 1, a->stats_shift);
+        if (!inorm_fast_fwd_ok(st, a, p.chunk, 1)) hipLaunchKernelGGL(inorm_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws, 1, a->stats_shift);
         return hipGetLastError() == hipSuccess ? SAVP_OK : SAVP_ELAUNCH;
     }
     if (use_large_plane_path(a)) {
@@ -438,7 +451,7 @@ extern "C" int savp_instnorm_act_fwd(void* stream, const SavpInormArgs* a) {
         dim3 grid((a->HW + p.chunk - 1) / p.chunk, a->N);
         size_t lds = (size_t)(NT / (a->C / 4)) * 2 * a->C * sizeof(float);
         hipLaunchKernelGGL(inorm_stats_kernel, grid, dim3(NT), lds, st, p, (double*)a->ws);
-        hipLaunchKernelGGL(inorm_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws, 0, (const float*)nullptr);
+        if (!inorm_fast_fwd_ok(st, a, p.chunk, 0)) hipLaunchKernelGGL(inorm_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws, 0, (const float*)nullptr);
         return hipGetLastError() == hipSuccess ? SAVP_OK : SAVP_ELAUNCH;
     }
     hipLaunchKernelGGL(inorm_fwd_kernel, dim3(a->N * (a->C / 4)), dim3(NT), 0, (hipStream_t)stream, p);
@@ -467,7 +480,7 @@ extern "C" int savp_instnorm_act_bwd(void* stream, const SavpInormArgs* a) {
         hipStream_t st = (hipStream_t)stream;
         p.chunk = inorm_chunk(a);
         dim3 grid((a->HW + p.chunk - 1) / p.chunk, a->N);
-        hipLaunchKernelGGL(inorm_bwd_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws);
+        if (!inorm_fast_bwd_ok(st, a, p.chunk)) hipLaunchKernelGGL(inorm_bwd_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws);
         return hipGetLastError() == hipSuccess ? SAVP_OK : SAVP_ELAUNCH;
     }
     if (use_large_plane_path(a)) {
@@ -477,7 +490,7 @@ extern "C" int savp_instnorm_act_bwd(void* stream, const SavpInormArgs* a) {
         dim3 grid((a->HW + p.chunk - 1) / p.chunk, a->N);
         size_t lds = (size_t)(NT / (a->C / 4)) * 2 * a->C * sizeof(float);
         hipLaunchKernelGGL(inorm_bwd_stats_kernel, grid, dim3(NT), lds, st, p, (double*)a->ws);
-        hipLaunchKernelGGL(inorm_bwd_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws);
+        if (!inorm_fast_bwd_ok(st, a, p.chunk)) hipLaunchKernelGGL(inorm_bwd_apply_kernel, grid, dim3(NT), 0, st, p, (const double*)a->ws);
         return hipGetLastError() == hipSuccess ? SAVP_OK : SAVP_ELAUNCH;
     }
     hipLaunchKernelGGL(inorm_bwd_kernel, dim3(a->N * (a->C / 4)), dim3(NT), 0, (hipStream_t)stream, p);

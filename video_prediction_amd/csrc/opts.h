@@ -23,6 +23,8 @@ enum SavpOptId {
     OPT_GATE_ALT,          // developer: conv_gate.hip's alternative tile instantiations (0)
     OPT_GATE_CELL,         // savp_convlstm_cell_fwd runs the whole cell in ONE launch where conv_gate.hip's tile holds whole images (1)
     OPT_GATE_WWARM,        // conv_gate.hip: workgroups of a column tile touch its weight block into their XCD's L2 first (1)
+    OPT_INORM_FAST,        // the coalesced instance norm's apply passes take the shape-specialised kernels of inorm_stream_*.hip where one covers the call (1; 0: the generic kernels, same bits; developer: 2 = the forward pass only)
+    OPT_INORM_FAST_TAKEN,  // counter, not a switch: apply passes launched on a shape-specialised kernel so far (a test can tell which path a call took)
     OPT_SPLITK_REDUCED,    // counter, not a switch: calls whose requested split-K count was cut (or dropped) because the caller's scratch was too small
     OPT_COUNT
 };
