@@ -340,7 +340,8 @@ int savp_tile_channels(void* stream, const float* z, int64_t R, int32_t HW, int3
 int savp_tile_channels_bf16(void* stream, const float* z, int64_t R, int32_t HW, int32_t C, float scale, SavpView out);
 /* out[(r,)c] += scale*sum_p in[r,p,c] (atomic accumulate; per_row keeps r) : bias grads, d(tile_concat), avg pool.
  * ws: optional caller-owned scratch of >= SAVP_COLSUM_WS_FLOATS floats (16-byte aligned, written before read): large all-pixel sums
- * then go through partial rows + one reduce launch instead of ~10^4 workgroups of atomics onto a few cache lines */
+ * then go through partial rows + one reduce launch instead of ~10^4 workgroups of atomics onto a few cache lines, and so do the all-row
+ * sums of narrow channel slices (C <= 16) when their R * 4 partial rows fit: added in a fixed order, the same bits every run */
 #define SAVP_COLSUM_WS_FLOATS (1024 * 4 * 256)
 int savp_colsum(void* stream, SavpView in, int64_t R, int32_t HW, int32_t C, float scale, float* out, int32_t per_row,
                 float* ws, int64_t ws_floats);
@@ -749,6 +750,27 @@ int savp_lpips_head(void* stream, const SavpLpipsHeadArgs* a);
 /* eval_diversity's running sum (base_model.py:194-198): div[f, b] += dv[f, s*B + b] for s = 0 .. n_valid-1 ascending with
  * 0 < base + s <= nd; ctl = {n_valid, base} in DEVICE memory; dv [F, S*B], div [F, B] contiguous. */
 int savp_lpips_diversity_add(void* stream, const float* dv, int32_t F, int32_t S, int32_t B, const int32_t* ctl, int32_t nd, float* div);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * TensorBoard summaries (summary.hip; video_prediction_amd/summaries.py writes the event file).
+ * ------------------------------------------------------------------------------------------------------------ */
+/* tensor_to_clip (utils/tf_utils.py:175-187) without an intermediate float tensor: the image board of the first n samples,
+ *     out[t, m * H + y, b * W + x, c] = u8(src[t * s_t + b * s_n + y * s_y + x * s_x + c * s_c + m * s_m])
+ * out: uint8 [T, M * H, n * W, C] contiguous, 4-byte aligned, every byte written; strides in elements (M = 1 for a 5-D tensor), so a batch
+ * window of a time-major activation, the [T1, N * HW, M] masks and the transformed images inside the mask convolution's input rows are
+ * read in place.  u8(v) = (uint8) trunc(min(max(v * 255.5f, 0), 255)) in float32 = tf.image.convert_image_dtype(float -> uint8,
+ * saturate=True) (unpinned: restated from memory); NaN -> 0.  SAVP_EINVAL without a launch (out untouched) when C is not 1 or 3 (a feature
+ * map: the reference skips it), a pointer is NULL, a dim is <= 0 or the board has 2^31 bytes or more. */
+int savp_summary_board_u8(void* stream, const float* src, int64_t s_t, int64_t s_n, int64_t s_y, int64_t s_x, int64_t s_c, int64_t s_m,
+                          int32_t T, int32_t n, int32_t H, int32_t W, int32_t C, int32_t M, uint8_t* out);
+/* tf_utils.flow_to_rgb (:588-603) as the flow transformation applies it per time step and unroll (savp_model.py:668-673).
+ * flows [T1, N, HW, row]: the K x components then the K y components in the first 2K channels of a row of `row` floats (SavpWarpArgs.flows).
+ * out [T1, N, HW, 3, K] contiguous.  mag = sqrt(x^2 + y^2), hue = (atan2(y, x) + pi) / 2 pi, saturation 1, value = (mag - min) / (max - min)
+ * with min / max over one step of one of the G equal batch groups (G = 2: the posterior and the prior unroll), then tf.image.hsv_to_rgb
+ * (unpinned: restated from memory).  max == min gives NaN like the reference.  minmax: 2 * T1 * G floats of scratch ({min, max} per
+ * (t, group) on return).  Two launches, no atomics, the result does not depend on the launch geometry. */
+int savp_flow_to_rgb(void* stream, const float* flows, int32_t T1, int32_t N, int32_t G, int32_t HW, int32_t K, int32_t row,
+                     float* minmax, float* out);
 
 /* Fold float64 accumulators into fp32 gradients (round 6): dst[i] += (float) src[i] ; src[i] = 0 for i in idx[0 .. n) (idx NULL: i = 0 .. n-1).
  * The parameter gradients that many workgroups add to are accumulated in a float64 twin of the gradient arena (SavpInormArgs.dgamma, ...)

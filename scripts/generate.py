@@ -127,10 +127,9 @@ def write_png(path, image):
 def write_gif(path, frames, fps):
     """frames uint8 [T, H, W, 1 | 3] -> an animated GIF at `fps`, looping (the reference's save_gif through moviepy, utils/ffmpeg_gif.py /
     generate.py:170-176; here Pillow's GIF encoder: adaptive palette per frame)."""
-    from PIL import Image
-    frames = np.ascontiguousarray(frames, dtype=np.uint8)
-    imgs = [Image.fromarray(f[..., 0], 'L') if f.shape[-1] == 1 else Image.fromarray(f, 'RGB') for f in frames]
-    imgs[0].save(path, save_all=True, append_images=imgs[1:], duration=max(1, int(round(1000.0 / max(fps, 1)))), loop=0)
+    from video_prediction_amd.summaries import encode_gif
+    with open(path, 'wb') as f:
+        f.write(encode_gif(frames, fps))
 
 
 def main(argv=None):

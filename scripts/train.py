@@ -10,15 +10,26 @@ Preserved from the reference (file:line under /root/reference/scripts/train.py):
   * the step loop: steps run from -1 (log without training) to max_steps - start_step, timing skips steps -1 and 0 (:241-245),
     the progress block every --progress_freq steps (:322-345, same lines: "progress  global step", "image/sec", d_loss / g_loss and
     their terms, learning_rate), checkpoints every --save_freq steps as <output_dir>/model-<global_step> (:347-350, max_to_keep 2).
-What TensorFlow did implicitly is explicit here: one `model.train_step(inputs)` is one `sess.run(model.train_op)`; summaries are
-JSON lines in <output_dir>/summaries.jsonl (scalars + best-of-N eval metrics) instead of TensorBoard event files; image / GIF
-summaries are not produced.  Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N` (one process per GPU,
+What TensorFlow did implicitly is explicit here: one `model.train_step(inputs)` is one `sess.run(model.train_op)`.
+Summaries (:247-321) go to two places.  <output_dir>/summaries.jsonl gets JSON lines: the training scalars every --summary_freq steps and
+one best-of-N row per --eval_summary_freq on a validation batch.  <output_dir>/events.out.tfevents.<time>.<host> is a TensorBoard event
+file (video_prediction_amd/summaries.py), opened at the first write: at --summary_freq the scalars of the training batch (losses, psnr /
+mse / ssim / lpips of a prior unroll, ground_truth_sampling_mean) and of a validation batch (tag suffix _1; metrics only: the losses
+exist only inside a train step here); at --image_summary_freq the GIF boards of images, gen_images, transformed_images, masks and
+gen_flows_rgb (+ _enc) for both batches, built on the GPU (csrc/summary.hip) and copied out as uint8 through a pinned buffer; at
+--eval_summary_freq the best / mean / worst GIF boards and metric scalars of eval_num_samples prior samples for both batches; at the
+multiples of --accum_eval_summary_freq the eval metrics averaged over num_examples_per_epoch() // batch_size validation batches
+(accum_..._1; unlike the reference not also at the last iteration, see should_accum_eval).  Not written: the pr_curve-hack plots,
+boards of gen_images_samples, the long_sequence_length model's accumulated evaluation, histograms, graph defs.  A summary pass changes
+no variable, Adam moment or noise stream, so a run's checkpoints do not depend on the frequencies.
+Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N` (one process per GPU,
 RCCL gradient exchange = --aggregate_nccl 1 of the reference; the per-GPU batch is batch_size / N like tf.split, base_model.py:523-527).
 `--dataset synthetic` (not in the reference) feeds seeded uniform video of --synthetic_shape without record files.
 """
 from __future__ import absolute_import, division, print_function
 
 import argparse
+import collections
 import errno
 import json
 import os
@@ -173,6 +184,19 @@ def should(step, freq, max_steps, start_step):
     return bool(freq and ((step + 1) % freq == 0 or (step + 1) in (0, max_steps - start_step)))
 
 
+def should_eval(step, freq, max_steps, start_step):
+    """train.py:236-238: never run eval summaries at the beginning since it's expensive, unless it's the last iteration."""
+    return should(step, freq, max_steps, start_step) and (step >= 0 or (step + 1) == (max_steps - start_step))
+
+
+def should_accum_eval(step, freq):
+    """The accumulated evaluation traverses the whole validation set with eval_num_samples draws per batch.  The reference also runs
+    it at the last iteration whatever the frequency (should_eval, train.py:301); here it runs only at the multiples of
+    --accum_eval_summary_freq: with the default of 100000 a run of a few steps would otherwise spend its time in that traversal.  A run
+    whose max_steps is a multiple of the frequency (the reference's recipes: 300000 / 100000) behaves the same."""
+    return bool(freq and step >= 0 and (step + 1) % freq == 0)
+
+
 def prune_checkpoints(output_dir, keep=2):
     """tf.train.Saver(max_to_keep=2), train.py:207."""
     import glob
@@ -262,6 +286,35 @@ def main(argv=None):
             out[k] = float(l)
         return out
 
+    # TensorBoard summaries (video_prediction_amd/summaries.py).  Every replica runs the summary passes (they touch no variable and no
+    # collective, so the replicas stay bit-identical); only the chief opens the event file, at its first write.  The validation batches
+    # of these summaries come from an iterator of their own: val_iter above keeps feeding the rows of summaries.jsonl as before.
+    from video_prediction_amd import summaries as S
+    event_writer, transfer, summary_iter = [None], S.BoardTransfer(), [None]
+
+    def next_summary_batch():
+        for _ in range(2):
+            if summary_iter[0] is None:
+                summary_iter[0] = iter(val_dataset.make_batch(per_gpu, device=device, rank=rank, world=world))
+            batch = next(summary_iter[0], None)
+            if batch is not None:
+                return batch
+            summary_iter[0] = None                  # a finite validation set ran out: start over
+        raise RuntimeError('the validation dataset delivers no batch')
+
+    def writer():
+        if event_writer[0] is None:
+            event_writer[0] = S.EventFileWriter(args.output_dir)
+        return event_writer[0]
+
+    def write_scalars(values, global_step, suffix=None):
+        if chief:
+            writer().add_scalars(collections.OrderedDict((k, float(v)) for k, v in values.items()), global_step, tag_suffix=suffix)
+
+    def write_gifs(boards, global_step, suffix=None):
+        if chief:                                   # uint8 boards, through the pinned staging buffer
+            writer().add_gifs(transfer.to_host(boards), global_step, tag_suffix=suffix)
+
     max_steps = model.hparams.max_steps
     start_step = model.global_step
     start_time = time.time()
@@ -308,6 +361,41 @@ def main(argv=None):
                                                 tag='eval_summary_1')) + '\n')
                 summaries.flush()
             print("done")
+        # TensorBoard event file (train.py:257-321): the training batch, then a validation batch with the tag suffix _1
+        do_summary = should(step, args.summary_freq, max_steps, start_step)
+        do_image = should(step, args.image_summary_freq, max_steps, start_step)
+        do_eval = should_eval(step, args.eval_summary_freq, max_steps, start_step)
+        do_accum = should_accum_eval(step, args.accum_eval_summary_freq)
+        if do_summary or do_image or do_eval:
+            val_inputs = next_summary_batch()        # one validation batch for the three, like the reference's single sess.run
+            if do_summary:
+                write_scalars(model.scalar_summary_fn(inputs, info), global_step)
+                write_scalars(model.scalar_summary_fn(val_inputs), global_step, '_1')
+            if do_image:
+                print("recording image summary")
+                write_gifs(model.image_summary_fn(inputs), global_step)
+                write_gifs(model.image_summary_fn(val_inputs), global_step, '_1')
+                print("done")
+            if do_eval:
+                for batch, suffix in ((inputs, None), (val_inputs, '_1')):
+                    boards, values = model.eval_summary_fn(batch)
+                    write_gifs(boards, global_step, suffix)
+                    write_scalars(values, global_step, suffix)
+        if do_accum:
+            model.accum_eval_reset()
+            # traverse (roughly up to rounding based on the batch size) all the validation dataset
+            num_updates = val_dataset.num_examples_per_epoch() // batch_size
+            for update_step in range(num_updates):
+                print('evaluating %d / %d' % (update_step + 1, num_updates))
+                model.accum_eval_update(next_summary_batch())
+            print("recording accum eval summary")
+            write_scalars(model.accum_eval_summary_fn(), global_step, '_1')
+            print("done")
+        if do_summary or do_image or do_eval or do_accum:
+            model.inputs = inputs
+            model.engine.set_images(inputs)                     # back to the training batch, as after the eval summary above
+            if event_writer[0] is not None:
+                event_writer[0].flush()
         if chief and should(step, args.progress_freq, max_steps, start_step):
             # global_step will have the correct step count if we resume from a checkpoint; it is read before it's incremented
             steps_per_epoch = train_dataset.num_examples_per_epoch() / batch_size
@@ -337,6 +425,8 @@ def main(argv=None):
             print("done")
     if summaries:
         summaries.close()
+    if event_writer[0] is not None:
+        event_writer[0].close()
     if dist is not None:
         dist.destroy_process_group()
 

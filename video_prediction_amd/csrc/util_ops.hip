@@ -106,7 +106,7 @@ __global__ __launch_bounds__(NT) void colsum_kernel(const float* __restrict__ in
 // and reduces over its pixel lanes in LDS.
 template <int V>
 __global__ __launch_bounds__(NT) void colsum_narrow_kernel(const float* __restrict__ in, long long sn, long long sp, int HW, int C,
-                                                           float scale, float* out, int per_row, int chunk) {
+                                                           float scale, float* out, int per_row, int chunk, float* part) {
     __shared__ float sh[NT * V];
     const int q = C / V;                              // lanes per pixel (power of two)
     const int cv = threadIdx.x & (q - 1), pl = threadIdx.x / q, npl = NT / q;
@@ -138,7 +138,8 @@ __global__ __launch_bounds__(NT) void colsum_narrow_kernel(const float* __restri
         for (int v = 0; v < V; ++v) {
             const float t = sh[threadIdx.x * V + v] * scale;
             const int c = cv * V + v;
-            if (per_row) unsafeAtomicAdd(out + r * C + c, t);
+            if (part) part[(r * gridDim.y + blockIdx.y) * C + c] = t;   // deterministic all-row sum: one partial row per workgroup, added up in row order by colsum_reduce_kernel
+            else if (per_row) unsafeAtomicAdd(out + r * C + c, t);
             else unsafeAtomicAdd(out + c, t);
         }
     }
@@ -220,9 +221,14 @@ extern "C" int savp_colsum(void* stream, SavpView in, int64_t R, int32_t HW, int
         if (chunk < per_pass) chunk = per_pass;
         dim3 grid((unsigned)R, (unsigned)((HW + chunk - 1) / chunk), 1u);
         hipStream_t st = (hipStream_t)stream;
-        if (V == 4) hipLaunchKernelGGL(colsum_narrow_kernel<4>, grid, dim3(NT), 0, st, (const float*)in.p, (long long)in.sn, (long long)in.sp, HW, C, scale, out, per_row, chunk);
-        else if (V == 2) hipLaunchKernelGGL(colsum_narrow_kernel<2>, grid, dim3(NT), 0, st, (const float*)in.p, (long long)in.sn, (long long)in.sp, HW, C, scale, out, per_row, chunk);
-        else hipLaunchKernelGGL(colsum_narrow_kernel<1>, grid, dim3(NT), 0, st, (const float*)in.p, (long long)in.sn, (long long)in.sp, HW, C, scale, out, per_row, chunk);
+        // all-row sums: with caller scratch every workgroup leaves its partial row there and the fixed-order reduce adds them up -- the same
+        // bits every run; without scratch (or per_row: a single writer per output) the workgroups add to `out` themselves
+        const long long prow = (long long)R * grid.y;
+        float* part = (!per_row && ws && (((uintptr_t)ws) & 15) == 0 && prow * C <= ws_floats && prow <= 0x7fffffffLL) ? ws : (float*)nullptr;
+        if (V == 4) hipLaunchKernelGGL(colsum_narrow_kernel<4>, grid, dim3(NT), 0, st, (const float*)in.p, (long long)in.sn, (long long)in.sp, HW, C, scale, out, per_row, chunk, part);
+        else if (V == 2) hipLaunchKernelGGL(colsum_narrow_kernel<2>, grid, dim3(NT), 0, st, (const float*)in.p, (long long)in.sn, (long long)in.sp, HW, C, scale, out, per_row, chunk, part);
+        else hipLaunchKernelGGL(colsum_narrow_kernel<1>, grid, dim3(NT), 0, st, (const float*)in.p, (long long)in.sn, (long long)in.sp, HW, C, scale, out, per_row, chunk, part);
+        if (part) hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)((C + 31) / 32)), dim3(NT), 0, st, (const float*)part, (int)prow, C, 1.f, out);
         return LAUNCH_OK();
     }
     // all-pixel sums of large pixel-linear tensors: partial rows in caller-owned scratch + reduce launch (see colsum_part_kernel);

@@ -1771,6 +1771,48 @@ def u8_frames_resize_f32(frames_u8, out_tm, crop):
               'savp_u8_frames_resize_f32')
 
 
+# TensorBoard summaries (csrc/summary.hip); the event-file writer is video_prediction_amd/summaries.py
+def summary_board_u8(src, out=None):
+    """tensor_to_clip (tf_utils.py:175-187) of src [T, n, H, W, C] or [T, n, H, W, C, M] -- any strided float32 view, read in place --
+    into the uint8 board out [T, M * H, n * W, C] (allocated when not given): out[t, m * H + y, b * W + x, c] = u8(src[t, b, y, x, c, m]),
+    u8 = tf.image.convert_image_dtype(uint8, saturate=True) (include/savp_hip.h).  C other than 1 or 3 is refused by the library
+    (RuntimeError, out untouched): the reference skips such tensors, and so do the callers."""
+    lib.require_device(src)
+    if src.dim() not in (5, 6):
+        raise ValueError('summary_board_u8: [T, n, H, W, C] or [T, n, H, W, C, M] expected, got %r' % (tuple(src.shape),))
+    T, n, H, W, C = src.shape[:5]
+    M = src.shape[5] if src.dim() == 6 else 1
+    st = list(src.stride()) + ([0] if src.dim() == 5 else [])
+    if out is None:
+        out = torch.empty(T, M * H, n * W, C, dtype=torch.uint8, device=src.device)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (T, M * H, n * W, C)):
+        raise ValueError('summary_board_u8: out must be a contiguous uint8 device tensor [%d, %d, %d, %d]' % (T, M * H, n * W, C))
+    lib.check(_L().savp_summary_board_u8(lib.stream(), src.data_ptr(), st[0], st[1], st[2], st[3], st[4], st[5], T, n, H, W, C, M,
+                                         out.data_ptr()), 'savp_summary_board_u8')
+    return out
+
+
+def flow_to_rgb(flows, K, groups=1, out=None, minmax=None):
+    """tf_utils.flow_to_rgb (:588-603) per time step and batch group (savp_model.py:668-673; include/savp_hip.h).  flows: contiguous
+    [T1, N, H, W, row] with the K x components then the K y components in the first 2K channels; out [T1, N, H, W, 3, K]; the magnitude
+    range is taken over one step of one of the `groups` equal slices of the batch.  max == min gives NaN, like the reference."""
+    lib.require_device(flows, out, minmax)
+    if flows.dim() != 5 or not flows.is_contiguous():
+        raise ValueError('flow_to_rgb: contiguous flows [T1, N, H, W, row] expected, got %r' % (tuple(flows.shape),))
+    T1, N, H, W, row = flows.shape
+    K, groups = int(K), int(groups)
+    if K < 1 or row < 2 * K or groups < 1 or N % groups:
+        raise ValueError('flow_to_rgb: K=%d / groups=%d do not fit flows %r' % (K, groups, tuple(flows.shape)))
+    if out is None:
+        out = torch.empty(T1, N, H, W, 3, K, device=flows.device)
+    if minmax is None:
+        minmax = torch.empty(T1 * groups, 2, device=flows.device)
+    if not (out.is_contiguous() and tuple(out.shape) == (T1, N, H, W, 3, K) and minmax.is_contiguous() and minmax.numel() >= 2 * T1 * groups):
+        raise ValueError('flow_to_rgb: out [T1, N, H, W, 3, K] and minmax [T1 * groups, 2], both contiguous, expected')
+    lib.check(_L().savp_flow_to_rgb(lib.stream(), _p(flows), T1, N, groups, H * W, K, row, _p(minmax), _p(out)), 'savp_flow_to_rgb')
+    return out
+
+
 def jpeg_args(info, n_frames, out_hw=None):
     """SavpJpegArgs for n_frames frames of the geometry `info` (io.SavpJpegInfo or a dict of its fields); pointers unset."""
     get = (lambda k: info[k]) if isinstance(info, dict) else (lambda k: getattr(info, k))

@@ -361,6 +361,8 @@ register('savp_lpips_stem', [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i3
 register('savp_lpips_maxpool3s2', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp])
 register('savp_lpips_head', [c_vp, ctypes.POINTER(SavpLpipsHeadArgs)])
 register('savp_lpips_diversity_add', [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp])
+register('savp_summary_board_u8', [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp])
+register('savp_flow_to_rgb', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp])
 register('savp_adam', [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp])
 register('savp_cdna_kernels_fwd', [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])
 register('savp_cdna_kernels_bwd', [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])

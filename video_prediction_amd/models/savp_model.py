@@ -451,9 +451,44 @@ class SAVPEngine(object):
                 if c1 > 0:
                     copy_view(z_post[:c1], [self.zs_all[:c1, B:]])
                 copy_view(self.d_prior, [self.zs_all[c1:, B:]])
-            return self.gen.forward(self.images_n, self.zs_all, gt, collect_masks=collect_masks, actions=self.actions_n,
-                                    states=self.states_n)
-        return self.gen.forward(self.images_n, None, gt, collect_masks=collect_masks, actions=self.actions_n, states=self.states_n)
+            gen = self.gen.forward(self.images_n, self.zs_all, gt, collect_masks=collect_masks, actions=self.actions_n,
+                                   states=self.states_n)
+        else:
+            gen = self.gen.forward(self.images_n, None, gt, collect_masks=collect_masks, actions=self.actions_n, states=self.states_n)
+        if collect_masks and hp.transformation == 'flow':
+            self._flows_to_rgb()
+        return gen
+
+    def _flows_to_rgb(self):
+        """gen_flows_rgb (savp_model.py:668-673): the reference's cell colours the flows of every step of each unroll by themselves, so the
+        magnitude range is that of one step of one half of the 2B batch.  Only with collect_masks=True (generator_fn, the image summary):
+        the flows of every step are in the unroll's own buffer anyway (tf_raw), the colours get theirs on first use; the train step and
+        the captured inference sequence run neither the launches nor own the buffer."""
+        g = self.gen
+        if getattr(self, 'flows_rgb', None) is None:
+            self.flows_rgb = torch.empty(g.T1, g.N, g.H, g.W, 3, g.nk, device=self.device)
+            self._flows_minmax = torch.empty(g.T1 * 2, 2, device=self.device)
+        K.flow_to_rgb(g.tf_raw.v, g.nk, groups=2 if self.nz else 1, out=self.flows_rgb, minmax=self._flows_minmax)
+
+    def output_views(self):
+        """The image-like outputs of the last forward_generator(collect_masks=True) as views of the engine's buffers, with the reference's
+        keys (savp_model.py:660-673): gen_images [T1, B, H, W, C], transformed_images [.., C, M], masks [.., 1, M] and, for
+        transformation='flow', gen_flows [.., 2, K] and gen_flows_rgb [.., 3, K]; with a latent also their '_enc' twins (the posterior
+        half of the 2B batch)."""
+        hp, g, B = self.hp, self.gen, self.B
+        C, M = self.image_shape[2], g.M
+        both = OrderedDict()
+        both['gen_images'] = g.gen.v
+        both['transformed_images'] = g.maskin.v[..., hp.ngf:hp.ngf + M * C].unflatten(-1, (M, C)).transpose(-1, -2)      # [..., C, M]
+        both['masks'] = g.masks.reshape(g.T1, g.N, g.H, g.W, 1, M)
+        if hp.transformation == 'flow':
+            both['gen_flows'] = g.tf_raw.v[..., :2 * g.nk].unflatten(-1, (2, g.nk))
+            both['gen_flows_rgb'] = self.flows_rgb
+        lo = B if self.nz else 0
+        out = OrderedDict((k, v[:, lo:]) for k, v in both.items())
+        if self.nz:
+            out.update((k + '_enc', v[:, :B]) for k, v in both.items())
+        return out
 
     # -- one sess.run(train_op) --------------------------------------------------------------------------------------------
     def _d_clips(self, D, phase, key_real, key_fake, fake_half, lo_real, lo_fake):
@@ -1157,6 +1192,10 @@ def generator_fn(inputs, mode, hparams, engine=None, noise=None, samples=False):
     outputs['gen_images'] = gen[:, lo:]
     outputs['transformed_images'] = timgs[:, lo:]
     outputs['masks'] = masks[:, lo:]
+    views = eng.output_views()
+    if hparams.transformation == 'flow':                          # savp_model.py:668-673
+        outputs['gen_flows'] = views['gen_flows']
+        outputs['gen_flows_rgb'] = views['gen_flows_rgb']
     gt = eng._gt_mask(noise)
     outputs['ground_truth_sampling_mean'] = gt[hparams.context_frames:, lo:].float().mean()
     if eng.ns:
@@ -1170,6 +1209,9 @@ def generator_fn(inputs, mode, hparams, engine=None, noise=None, samples=False):
         outputs['gen_images_enc'] = gen[:, :B]
         outputs['transformed_images_enc'] = timgs[:, :B]
         outputs['masks_enc'] = masks[:, :B]
+        if hparams.transformation == 'flow':
+            outputs['gen_flows_enc'] = views['gen_flows_enc']
+            outputs['gen_flows_rgb_enc'] = views['gen_flows_rgb_enc']
         outputs['ground_truth_sampling_mean_enc'] = gt[hparams.context_frames:, :B].float().mean()
         if eng.ns:
             outputs['gen_states_enc'] = g.gen_states.v[:, :B]
@@ -1307,6 +1349,91 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
             num_samples_for_diversity=(self.eval_num_samples_for_diversity if num_samples_for_diversity is None
                                        else num_samples_for_diversity))
         return self.eval_outputs, self.eval_metrics
+
+    # -- summaries (base_model.py:694-731; written by video_prediction_amd.summaries, driven by scripts/train.py) ----------------------------
+    # Every pass below runs eagerly on the engine's buffers, outside any hipGraph capture, and is invisible to training: it reads the
+    # variables (the generator's weight preparation is a pure function of them), changes no Adam moment, and its random draws come from
+    # generators seeded by (seed, rank, step, stream), never from a stream a later train_step continues.  What it does overwrite is the
+    # staged batch, the staged noise and the activations, all of which the next train_step writes before it reads; a caller that passed
+    # `inputs` and wants the training batch's conditioning back stages it again (engine.set_images), as scripts/train.py does.
+    # Not reproduced: the pr_curve-hack plot summaries (they need a patched TensorBoard), boards of gen_images_samples,
+    # the second long_sequence_length model of the accumulated evaluation, histograms and graph defs.
+    SUMMARY_MAX_OUTPUTS = 8                                        # add_gif_summaries(max_outputs=8), tf_utils.py:229-236
+
+    def _stage(self, inputs):
+        if inputs is not None:
+            refuse_conditioning_inputs(inputs)
+            self.inputs = inputs
+        self.engine.set_images(self.inputs)
+
+    def scalar_summary_fn(self, inputs=None, info=None):
+        """`summary_op` (base_model.py:704-715): {name: device scalar or number} of every d_losses / g_losses term, d_loss, g_loss,
+        loss = d_loss + g_loss (from `info`, the dict of the train step just run; omitted without one: the losses exist only inside a
+        step here), the metrics_fn results (psnr, mse, ssim, and lpips when its weights are configured) of a prior unroll on `inputs`
+        (default: the current batch) and the 0-d generator outputs ground_truth_sampling_mean(_enc)."""
+        eng = self.engine
+        out = OrderedDict()
+        if info is not None:
+            for k, (l, _) in list(info['d_losses'].items()) + list(info['g_losses'].items()):
+                out[k] = l
+            out['d_loss'], out['g_loss'] = info['d_loss'], info['g_loss']        # d_loss is 0 without a discriminator (the reference omits it then)
+            out['loss'] = info['d_loss'] + info['g_loss']
+        self._stage(inputs)
+        noise = eng.default_noise()
+        gen = eng.generate(noise)
+        out.update(eng.metrics(gen))
+        gt = eng._gt_mask(noise)[eng.hp.context_frames:]
+        out['ground_truth_sampling_mean'] = gt[:, eng.B if eng.nz else 0:].float().mean()
+        if eng.nz:
+            out['ground_truth_sampling_mean_enc'] = gt[:, :eng.B].float().mean()
+        return out
+
+    def image_summary_fn(self, inputs=None, noise=None):
+        """`image_summary_op` (add_summaries on the inputs and outputs, base_model.py:702-703,716): the GIF boards (tensor_to_clip,
+        tf_utils.py:175-187) of `images`, gen_images, transformed_images, masks, gen_flows_rgb and their '_enc' twins for the first
+        min(B, 8) samples, built by the board kernel straight from the engine's buffers: {name: uint8 device tensor [T, M * H, n * W, C]}.
+        Tensors whose channel axis is not 1 or 3 (gen_flows) are skipped as feature maps, like the reference does."""
+        eng = self.engine
+        self._stage(inputs)
+        eng.prep_generator_weights()
+        eng.forward_generator(eng.default_noise() if noise is None else noise, collect_masks=True)
+        n = min(eng.B, self.SUMMARY_MAX_OUTPUTS)
+        boards = OrderedDict()
+        boards['images'] = K.summary_board_u8(eng.images_tm[:, :n])
+        for k, v in eng.output_views().items():
+            if v.shape[4] in (1, 3):
+                boards[k] = K.summary_board_u8(v[:, :n])
+        return boards
+
+    def eval_summary_fn(self, inputs=None, num_samples=None, noises=None):
+        """`eval_summary_op` (base_model.py:718-724): runs eval_outputs_and_metrics_fn on `inputs` and returns (boards, scalars): a GIF
+        board of every eval_outputs entry (first min(B, 8) samples) and, per eval_metrics entry, its mean over batch and time (the scalar
+        half of add_plot_and_scalar_summaries)."""
+        outs, mets = self.eval_outputs_and_metrics_fn(inputs, num_samples=num_samples, noises=noises)
+        n = min(self.engine.B, self.SUMMARY_MAX_OUTPUTS)
+        boards = OrderedDict((k, K.summary_board_u8(v[:, :n])) for k, v in outs.items() if v.dim() in (5, 6) and v.shape[4] in (1, 3))
+        return boards, OrderedDict((k, v.mean()) for k, v in mets.items())
+
+    def accum_eval_reset(self):
+        """`accum_eval_metrics_reset_op` (base_model.py:694-699)."""
+        self._accum_eval, self._accum_eval_count = OrderedDict(), 0
+
+    def accum_eval_update(self, inputs=None, num_samples=None, noises=None):
+        """One update of tf.metrics.mean_tensor over eval_metrics (base_model.py:695-697): total += value, count += 1."""
+        if getattr(self, '_accum_eval', None) is None:
+            self.accum_eval_reset()
+        _, mets = self.eval_outputs_and_metrics_fn(inputs, num_samples=num_samples, noises=noises)
+        for k, v in mets.items():
+            if k in self._accum_eval:
+                self._accum_eval[k] += v
+            else:
+                self._accum_eval[k] = v.clone()
+        self._accum_eval_count += 1
+
+    def accum_eval_summary_fn(self):
+        """`accum_eval_summary_op` (base_model.py:726-731): {'accum_<name>': mean over batch and time of the running mean tensor}."""
+        n = float(max(1, getattr(self, '_accum_eval_count', 0)))
+        return OrderedDict(('accum_' + k, (v / n).mean()) for k, v in (getattr(self, '_accum_eval', None) or {}).items())
 
     def restore(self, checkpoints, restore_to_checkpoint_mapping=None):
         """savp_model.py:848-855 / base_model.py:229-247: `checkpoints` is a TensorFlow V2 checkpoint directory or prefix (or a
