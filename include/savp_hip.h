@@ -799,6 +799,52 @@ int64_t savp_gate_weights_bytes(int32_t taps, int32_t Cx, int32_t Cy);
 int savp_pack_gate_weights(void* stream, const float* src, int32_t taps, int32_t Cx, int32_t Cy, void* out, int32_t interleave);   /* interleave: see SavpConvArgs.w_frag_il */
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Designated-pixel distributions (pix_distribs.hip): inputs['pix_distribs'] of SAVPCell.call (savp_model.py:252-255,288-290,350-351,
+ * 408-410,598-621,648-653,663-665,681-683).  They never feed back into the image path and no loss reads them, so ONE launch runs the
+ * whole recurrence over the T1 steps of an unroll that has already run, from what the unroll keeps per step:
+ *     cur_t   = gt_mask[t, n] ? pix_in[t, n] : gen[t-1, n]                      (gen[-1] = 0)
+ *     last_t  = last_{t-1}[1:] + [cur_t]                                         (last_{-1} = [pix_in[0]] * nsrc)
+ *     slot_m  = TRANSFORMED: kernel / flow m (group m / K applied to source last_t[m / K]; CDNA / DNA kernels on the SYMMETRIC-padded
+ *               map, flows as flow_ops.image_warp): exactly the first nsrc * K slots, in order, arg = m, as apply_kernels / apply_flows
+ *               return them | behind them CURRENT: cur_t | FIXED: pix_in[arg] | LAST_CONTEXT: pix_in[min(t, context_frames - 1)]
+ *     gen[t]  = sum_m slot_m * mask_m ;  gen[t] /= sum over (H, W) of gen[t]     (no epsilon: a zero sum gives NaN like the reference)
+ * mask = softmax(logits) over the M slots recomputed in fp32, or `logits` itself when masks_given.  One workgroup per (sample, designated
+ * pixel) map; the nsrc source maps and the new map stay in LDS where (nsrc + 1) * H * W floats fit beside a 1.3 KB header in 160 KB
+ * (savp_pix_distribs_lds_resident answers 1, a host-side predicate), otherwise -- or with force_global, a developer switch -- the sources are
+ * read from the pix_in / gen rows in global memory.  The normalising sum is a fixed-order in-workgroup reduction: no atomics, the same bits
+ * in every run and on either path's own terms.
+ * Views: pix_in [T_in >= T1, N, H, W, P], gen [T1, N, H, W, P] and logits by step / sample / pixel strides in elements (channel stride 1;
+ * channel p of pix_in / gen is map p, the first M channels of a logits pixel are the slots); tfp = the step's transformation parameters:
+ * CDNA kernels [kh * kw][nsrc * K] per (step, sample) (tf_sp unused, kh * kw * nsrc * K <= 256), normalised DNA kernels with the same
+ * row per pixel, or flows per pixel with the nsrc * K x components before the y components (SavpWarpArgs.flows).  transformed: NULL or
+ * [T1, N, H, W, P, M] contiguous, every element written.  nsrc <= SAVP_MAX_SOURCES, M <= SAVP_PIX_MAX_SLOTS; FIXED frames must be < T_in.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SAVP_PIX_MAX_SLOTS 16
+enum { SAVP_PIX_TF_CDNA = 0, SAVP_PIX_TF_DNA = 1, SAVP_PIX_TF_FLOW = 2 };
+enum { SAVP_PIX_SLOT_TRANSFORMED = 0, SAVP_PIX_SLOT_CURRENT = 1, SAVP_PIX_SLOT_FIXED = 2, SAVP_PIX_SLOT_LAST_CONTEXT = 3 };
+typedef struct {
+    int32_t T1, N, H, W, P;
+    int32_t tf, kh, kw, nsrc, K;             /* nsrc = last_frames, K = num_transformed_images (kernels / flows per source) */
+    int32_t context_frames, T_in;
+    int32_t M;
+    int32_t slot_kind[SAVP_PIX_MAX_SLOTS];
+    int32_t slot_arg[SAVP_PIX_MAX_SLOTS];
+    int32_t masks_given, force_global;
+    const float* pix_in; int64_t pi_st, pi_sn, pi_sp;
+    const int32_t* gt_mask;                   /* [T1, N] contiguous */
+    const float* tfp; int64_t tf_st, tf_sn, tf_sp;
+    const float* logits; int64_t lg_st, lg_sn, lg_sp;
+    float* gen; int64_t g_st, g_sn, g_sp;
+    float* transformed;
+} SavpPixDistribArgs;
+int savp_pix_distribs_fwd(void* stream, const SavpPixDistribArgs* a);
+int savp_pix_distribs_lds_resident(const SavpPixDistribArgs* a);
+/* tf_utils.pixel_distribution (tf_utils.py:562-585) as softmotion_dataset.py:62-68 applies it: pos [rows, P, 2] = (y, x) per designated pixel,
+ * out [rows, H, W, P] contiguous, every element written.  A one-hot on the FLAT index y * W + x of each of the four corners (x1 == W lands at
+ * the start of the next row; an index outside [0, H * W) contributes nothing) times its fp32 bilinear weight (x1 - x) * (y1 - y), ... */
+int savp_pixel_distribution(void* stream, const float* pos, int64_t rows, int32_t P, int32_t H, int32_t W, float* out);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Developer / soak-test aids (debug_ops.hip; no reference counterpart, no product caller): make what a correct launch sequence must never
  * read adversarial.  savp_debug_poison_lds fills all 160 KB of LDS of every CU with `pattern` (0xFFFFFFFF = NaN as fp32, bf16 and fp64);
  * `sink` (one uint32 of device memory, or NULL) counts words that did not read back.  savp_debug_fill_u32 fills `words` 32-bit words of

@@ -12,8 +12,8 @@ from .softmotion_dataset import SoftmotionVideoDataset
 
 
 class CartgripperVideoDataset(SoftmotionVideoDataset):
-    def __init__(self, input_dir, mode='train', num_epochs=None, seed=None, hparams_dict=None, hparams=None):
-        self._open(input_dir, mode, num_epochs, seed, hparams_dict, hparams)
+    def __init__(self, input_dir, mode='train', num_epochs=None, seed=None, hparams_dict=None, hparams=None, pix_distribs=None):
+        self._open(input_dir, mode, num_epochs, seed, hparams_dict, hparams, pix_distribs=pix_distribs)
         self.image_key_fmt = '%d/image_view0/encoded'                                 # cartgripper_dataset.py:10
         self.image_shape = (48, 64, 3)
         _, buf = sio.example_feature(self._first, self.image_key_fmt % 0)

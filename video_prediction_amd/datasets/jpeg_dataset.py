@@ -56,10 +56,7 @@ class JpegVideoDataset(SoftmotionVideoDataset):
         hp = self.hparams
         shuffle = self.mode == 'train' or (self.mode == 'val' and hp.shuffle_on_val)        # base_dataset.py:131
         time_shift = hp.time_shift if ((hp.time_shift and self.mode == 'train') or hp.force_time_shift) else 0   # :198
-        float_keys = []
-        if hp.use_state:
-            (s_fmt, s_shape), (a_fmt, a_shape) = self.state_like_names_and_shapes['states'], self.action_like_names_and_shapes['actions']
-            float_keys = [(s_fmt, s_shape[0], 0), (a_fmt, a_shape[0], 1)]
+        float_keys = self._float_keys()
         files, seed = self._shard(rank, world)
         return sio.VideoPipeline(files, self.image_key_fmt, self._max_sequence_length, self.image_shape,
                                  hp.sequence_length, batch_size, frame_skip=hp.frame_skip, time_shift=time_shift, shuffle=shuffle,
@@ -122,9 +119,6 @@ class _JpegBatchIterator(object):
         else:
             self.K.u8_frames_resize_f32(self.dev_u8, images_tm, cs[0])
         out = {'images': images_tm.transpose(0, 1)}                      # batch-major view, like the reference's iterator
-        if floats:
-            out['states'] = torch.from_numpy(floats[0]).to(self.device)
-            out['actions'] = torch.from_numpy(floats[1]).to(self.device)
-        return out
+        return self.ds._float_outputs(floats, out, self.K, self.device)
 
     next = __next__

@@ -2,7 +2,14 @@
 (video_prediction/datasets/softmotion_dataset.py:11-82, base_dataset.py:12-232,235-353) on libsavp_io.so:
 C++ TFRecord reading / Example parsing / sub-sequence sampling / shuffling / batching / prefetch, uint8 over PCIe,
 conversion to float32 [0,1] on the GPU.  Frames here are raw uint8 (jpeg_encoding False); the JPEG-encoded datasets build on this class in
-jpeg_dataset.py.  Not supported (raise): object_pos pixel distributions.
+jpeg_dataset.py.
+
+object_pos pixel distributions (softmotion_dataset.py:42-43,62-68) are opt-in: SoftmotionVideoDataset(..., pix_distribs=True) or
+SAVP_PIX_DISTRIBS=1 in the environment.  With it, and when the first example has '%d/object_pos' (2P floats per frame: (y, x) of P
+designated pixels), a batch also carries 'pix_distribs' [B, T, H, W, P], built on the device by savp_pixel_distribution (tf_utils.
+pixel_distribution restated: a bilinear one-hot on the flat index y * W + x).  Without the opt-in, or without object_pos in the records,
+no such key is emitted.  Together with crop_size / scale_size it raises: the reference would yield maps of the records' size beside
+resized images.
 
 crop_size / scale_size (base_dataset.py:63-64,85-86,159-184).  The records are read and cross PCIe at the size they were recorded
 (image_shape); when either hyper-parameter is set the conversion kernel also centre-crops or zero-pads every frame to crop x crop
@@ -28,8 +35,8 @@ from ..hparams import HParams
 
 
 class SoftmotionVideoDataset(object):
-    def __init__(self, input_dir, mode='train', num_epochs=None, seed=None, hparams_dict=None, hparams=None):
-        self._open(input_dir, mode, num_epochs, seed, hparams_dict, hparams)
+    def __init__(self, input_dir, mode='train', num_epochs=None, seed=None, hparams_dict=None, hparams=None, pix_distribs=None):
+        self._open(input_dir, mode, num_epochs, seed, hparams_dict, hparams, pix_distribs=pix_distribs)
         # infer the image feature name, frames per example and image shape from the first example (softmotion_dataset.py:15-43,
         # base_dataset.py:264-312)
         first = self._first
@@ -58,8 +65,13 @@ class SoftmotionVideoDataset(object):
     def _count_frames(names, image_name):
         return 1 + max(int(m.group(1)) for m in (re.match(r'(\d+)/%s/encoded' % image_name, n) for n in names) if m)
 
-    def _open(self, input_dir, mode, num_epochs, seed, hparams_dict, hparams):
-        """base_dataset.py:13-58: input_dir holds train/ val/ test/ sub-directories of *.tfrecord* files (or is one of them)."""
+    object_pos_fmt = '%d/object_pos'                  # softmotion_dataset.py:43
+    pix_distribs = False                              # the opt-in; set by _open (a subclass that opens its files itself has none)
+
+    def _open(self, input_dir, mode, num_epochs, seed, hparams_dict, hparams, pix_distribs=None):
+        """base_dataset.py:13-58: input_dir holds train/ val/ test/ sub-directories of *.tfrecord* files (or is one of them).
+        pix_distribs: the opt-in of the object_pos pixel distributions (None: SAVP_PIX_DISTRIBS=1 in the environment)."""
+        self.pix_distribs = bool(pix_distribs) if pix_distribs is not None else os.environ.get('SAVP_PIX_DISTRIBS', '0') == '1'
         self.input_dir = os.path.normpath(os.path.expanduser(input_dir))
         self.mode = mode
         self.num_epochs = num_epochs
@@ -90,6 +102,42 @@ class SoftmotionVideoDataset(object):
             return None
         crop = hp.crop_size or min(self.image_shape[:2])
         return crop, (hp.scale_size or crop)
+
+    @property
+    def num_designated_pixels(self):
+        """P of batch['pix_distribs']: half the width of the first example's object_pos feature; 0 without the opt-in or without the
+        feature (softmotion_dataset.py:42-43: the shape is inferred from the first example)."""
+        if not self.pix_distribs or (self.object_pos_fmt % 0) not in self._feature_names(self._first):
+            return 0
+        kind, vals = sio.example_feature(self._first, self.object_pos_fmt % 0)
+        if kind != 2 or not vals or len(vals) % 2:
+            raise ValueError('%s: expected (y, x) float pairs, got %r' % (self.object_pos_fmt % 0, vals))
+        if self.crop_and_scale is not None or getattr(self, 'random_crop', 0):
+            raise NotImplementedError('object_pos pixel distributions with crop_size / scale_size (or a random crop): the maps would keep '
+                                      'the size of the records beside resized images')
+        return len(vals) // 2
+
+    def _float_keys(self):
+        """[(key format, width, 0 = one per frame | 1 = one per transition)] of the pipeline: states, actions, then object_pos."""
+        float_keys = []
+        if self.hparams.use_state:
+            (s_fmt, s_shape), (a_fmt, a_shape) = self.state_like_names_and_shapes['states'], self.action_like_names_and_shapes['actions']
+            float_keys = [(s_fmt, s_shape[0], 0), (a_fmt, a_shape[0], 1)]
+        P = self.num_designated_pixels
+        if P:
+            float_keys.append((self.object_pos_fmt, 2 * P, 0))
+        return float_keys
+
+    def _float_outputs(self, floats, out, K, device):
+        """The float features of one batch into the inputs dict: states / actions as read, object_pos as pix_distribs [B, T, H, W, P]."""
+        floats = list(floats or [])
+        if self.hparams.use_state:
+            out['states'] = torch.from_numpy(floats.pop(0)).to(device)
+            out['actions'] = torch.from_numpy(floats.pop(0)).to(device)
+        if floats:
+            H, W = self.output_image_shape[:2]
+            out['pix_distribs'] = K.pixel_distribution(torch.from_numpy(floats.pop(0)).to(device), H, W)
+        return out
 
     @property
     def output_image_shape(self):
@@ -170,10 +218,7 @@ class SoftmotionVideoDataset(object):
         hp = self.hparams
         shuffle = self.mode == 'train' or (self.mode == 'val' and hp.shuffle_on_val)        # base_dataset.py:131
         time_shift = hp.time_shift if ((hp.time_shift and self.mode == 'train') or hp.force_time_shift) else 0   # :198
-        float_keys = []
-        if hp.use_state:
-            (s_fmt, s_shape), (a_fmt, a_shape) = self.state_like_names_and_shapes['states'], self.action_like_names_and_shapes['actions']
-            float_keys = [(s_fmt, s_shape[0], 0), (a_fmt, a_shape[0], 1)]
+        float_keys = self._float_keys()
         files, seed = self._shard(rank, world)
         return sio.VideoPipeline(files, self.image_key_fmt, self._max_sequence_length, self.image_shape,
                                  hp.sequence_length, batch_size, frame_skip=hp.frame_skip, time_shift=time_shift, shuffle=shuffle,
@@ -184,7 +229,7 @@ class SoftmotionVideoDataset(object):
 
     def make_batch(self, batch_size, device='cuda:0', rank=0, world=1):
         """base_dataset.py:153-156: an iterator of input dicts {'images': float32 [B,T,H,W,C] in [0,1] on the device, ('states',
-        'actions')}.  Frames cross PCIe as uint8 from pinned memory; conversion + layout change happen in one HIP kernel.
+        'actions', 'pix_distribs')}.  Frames cross PCIe as uint8 from pinned memory; conversion + layout change happen in one HIP kernel.
         rank / world: the data-parallel replica this iterator feeds (see _shard)."""
         return _BatchIterator(self, batch_size, device, rank, world)
 
@@ -226,9 +271,6 @@ class _BatchIterator(object):
         else:
             self.K.u8_frames_resize_f32(self.dev_u8, images_tm, cs[0])
         out = {'images': images_tm.transpose(0, 1)}                      # batch-major view, like the reference's iterator
-        if floats:
-            out['states'] = torch.from_numpy(floats[0]).to(self.device)
-            out['actions'] = torch.from_numpy(floats[1]).to(self.device)
-        return out
+        return self.ds._float_outputs(floats, out, self.K, self.device)
 
     next = __next__

@@ -1028,6 +1028,88 @@ def state_pred_bwd(gt, W, sa, dgen, dW64, db64):
               'savp_state_pred_bwd')
 
 
+def _pix_strides(t, what, pixel_dims=True):
+    """(step, sample, pixel) element strides of a time-major view [T, N, H, W, C] (pixel_dims) or [T, N, ...contiguous row]."""
+    lib.require_device(t)
+    if pixel_dims:
+        if t.dim() != 5 or (t.shape[4] != 1 and t.stride(4) != 1) or (t.shape[2] != 1 and t.stride(2) != t.shape[3] * t.stride(3)):
+            raise ValueError('%s: expected a [T, N, H, W, C] view with channel stride 1 and pixel-linear rows, got shape %s stride %s'
+                             % (what, tuple(t.shape), t.stride()))
+        return t.stride(0), t.stride(1), t.stride(3)
+    if not t[0, 0].is_contiguous():
+        raise ValueError('%s: the row of one (step, sample) must be contiguous' % what)
+    return t.stride(0), t.stride(1), 0
+
+
+def _pix_args(pix_in, gt_mask, tf, tfp, logits, gen, slots, nsrc, K, context_frames, kh, kw, transformed, masks_given, force_global):
+    a = lib.SavpPixDistribArgs()
+    T1, N, H, W, P = gen.shape
+    a.T1, a.N, a.H, a.W, a.P = T1, N, H, W, P
+    a.tf, a.kh, a.kw, a.nsrc, a.K = lib.PIX_TF[tf], int(kh), int(kw), int(nsrc), int(K)
+    a.context_frames, a.T_in = int(context_frames), pix_in.shape[0]
+    if not 1 <= len(slots) <= lib.PIX_MAX_SLOTS:
+        raise ValueError('1 .. %d slots, got %d' % (lib.PIX_MAX_SLOTS, len(slots)))
+    a.M = M = len(slots)
+    for m, (kind, arg) in enumerate(slots):
+        a.slot_kind[m], a.slot_arg[m] = int(kind), int(arg)
+    a.masks_given, a.force_global = int(bool(masks_given)), int(bool(force_global))
+    nk = nsrc * K
+    if tuple(pix_in.shape[1:]) != (N, H, W, P) or pix_in.shape[0] < T1:
+        raise ValueError('pix_in: expected [>= %d, %d, %d, %d, %d], got %s' % (T1, N, H, W, P, tuple(pix_in.shape)))
+    _require_i32(gt_mask)
+    if tuple(gt_mask.shape) != (T1, N) or not gt_mask.is_contiguous():
+        raise ValueError('gt_mask: expected contiguous int32 [%d, %d]' % (T1, N))
+    want = {'cdna': (T1, N, kh * kw, nk), 'dna': (T1, N, H, W, kh * kw * nk), 'flow': (T1, N, H, W, 2 * nk)}[tf]
+    if tuple(tfp.shape[:-1]) != want[:-1] or tfp.shape[-1] < want[-1] or (tf != 'flow' and tfp.shape[-1] != want[-1]):
+        raise ValueError('%s parameters: expected %s, got %s' % (tf, want, tuple(tfp.shape)))
+    if tuple(logits.shape[:4]) != (T1, N, H, W) or logits.shape[4] < M:
+        raise ValueError('logits / masks: expected [%d, %d, %d, %d, >= %d], got %s' % (T1, N, H, W, M, tuple(logits.shape)))
+    a.pix_in = _p(pix_in)
+    a.pi_st, a.pi_sn, a.pi_sp = _pix_strides(pix_in, 'pix_in')
+    a.gt_mask = _p(gt_mask)
+    a.tfp = _p(tfp)
+    a.tf_st, a.tf_sn, a.tf_sp = _pix_strides(tfp, tf + ' parameters', pixel_dims=tf != 'cdna')
+    a.logits = _p(logits)
+    a.lg_st, a.lg_sn, a.lg_sp = _pix_strides(logits, 'logits')
+    a.gen = _p(gen)
+    a.g_st, a.g_sn, a.g_sp = _pix_strides(gen, 'gen')
+    if transformed is not None:
+        lib.require_device(transformed)
+        if tuple(transformed.shape) != (T1, N, H, W, P, M) or not transformed.is_contiguous():
+            raise ValueError('transformed: expected contiguous [%d, %d, %d, %d, %d, %d]' % (T1, N, H, W, P, M))
+        a.transformed = _p(transformed)
+    return a
+
+
+def pix_distribs_fwd(pix_in, gt_mask, tf, tfp, logits, gen, slots, nsrc, K, context_frames, kh=1, kw=1, transformed=None,
+                     masks_given=False, force_global=False):
+    """savp_pix_distribs_fwd (include/savp_hip.h): the designated-pixel distributions of a whole unroll in one launch.  pix_in
+    [>= T1, N, H, W, P], gt_mask int32 [T1, N], tf in ('cdna', 'dna', 'flow') with tfp the unroll's per-step CDNA kernels [T1, N, kh*kw, nsrc*K],
+    normalised DNA kernels [T1, N, H, W, kh*kw*nsrc*K] or flows [T1, N, H, W, >= 2*nsrc*K]; logits [T1, N, H, W, >= M] (masks with
+    masks_given); slots = [(lib.PIX_SLOT_*, arg)] in the reference's order; fills gen [T1, N, H, W, P] and, when given, transformed
+    [T1, N, H, W, P, M].  Returns True when the maps were LDS resident, False when the sources were read from global memory."""
+    a = _pix_args(pix_in, gt_mask, tf, tfp, logits, gen, slots, nsrc, K, context_frames, kh, kw, transformed, masks_given, force_global)
+    resident = bool(lib.get_raw().savp_pix_distribs_lds_resident(ctypes.byref(a)))
+    lib.check(_L().savp_pix_distribs_fwd(lib.stream(), ctypes.byref(a)), 'savp_pix_distribs_fwd')
+    return resident
+
+
+def pixel_distribution(pos, H, W, out=None):
+    """tf_utils.pixel_distribution over any leading dims: pos [..., 2P] = (y, x) per designated pixel -> [..., H, W, P]."""
+    lib.require_device(pos)
+    if pos.shape[-1] % 2 or not pos.shape[-1]:
+        raise ValueError('positions are (y, x) pairs, got a last dim of %d' % pos.shape[-1])
+    pos = pos.contiguous()
+    P = pos.shape[-1] // 2
+    lead = tuple(pos.shape[:-1])
+    if out is None:
+        out = torch.empty(lead + (H, W, P), device=pos.device)
+    lib.require_device(out)
+    assert out.is_contiguous() and tuple(out.shape) == lead + (H, W, P)
+    lib.check(_L().savp_pixel_distribution(lib.stream(), _p(pos), pos.numel() // (2 * P), P, H, W, _p(out)), 'savp_pixel_distribution')
+    return out
+
+
 def adam(p, g, m, v, lr_t, beta1, beta2, eps=1e-8, gscale=1.0, lr_t_dev=None):
     """lr_t_dev: optional 1-element device tensor that overrides lr_t (graph replays with a changing rate)."""
     lib.check(_L().savp_adam(lib.stream(), p.numel(), _p(p), _p(g), _p(m), _p(v), float(lr_t), float(beta1), float(beta2),

@@ -476,6 +476,31 @@ register('savp_tv_loss', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, 
 register('savp_state_pred_fwd', [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 7)
 register('savp_state_pred_bwd', [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 6)
 register('savp_pack_gate_weights', [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32])
+
+PIX_MAX_SLOTS = 16                # SAVP_PIX_MAX_SLOTS
+PIX_TF = {'cdna': 0, 'dna': 1, 'flow': 2}                                    # SAVP_PIX_TF_*
+PIX_SLOT_TRANSFORMED, PIX_SLOT_CURRENT, PIX_SLOT_FIXED, PIX_SLOT_LAST_CONTEXT = 0, 1, 2, 3
+
+
+class SavpPixDistribArgs(ctypes.Structure):
+    _fields_ = [
+        ('T1', c_i32), ('N', c_i32), ('H', c_i32), ('W', c_i32), ('P', c_i32),
+        ('tf', c_i32), ('kh', c_i32), ('kw', c_i32), ('nsrc', c_i32), ('K', c_i32),
+        ('context_frames', c_i32), ('T_in', c_i32),
+        ('M', c_i32), ('slot_kind', c_i32 * PIX_MAX_SLOTS), ('slot_arg', c_i32 * PIX_MAX_SLOTS),
+        ('masks_given', c_i32), ('force_global', c_i32),
+        ('pix_in', c_vp), ('pi_st', c_i64), ('pi_sn', c_i64), ('pi_sp', c_i64),
+        ('gt_mask', c_vp),
+        ('tfp', c_vp), ('tf_st', c_i64), ('tf_sn', c_i64), ('tf_sp', c_i64),
+        ('logits', c_vp), ('lg_st', c_i64), ('lg_sn', c_i64), ('lg_sp', c_i64),
+        ('gen', c_vp), ('g_st', c_i64), ('g_sn', c_i64), ('g_sp', c_i64),
+        ('transformed', c_vp),
+    ]
+
+
+register('savp_pix_distribs_fwd', [c_vp, ctypes.POINTER(SavpPixDistribArgs)])
+register('savp_pix_distribs_lds_resident', [ctypes.POINTER(SavpPixDistribArgs)])
+register('savp_pixel_distribution', [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp])
 register('savp_debug_poison_lds', [c_vp, ctypes.c_uint32, c_vp])
 register('savp_debug_fill_u32', [c_vp, c_vp, c_i64, ctypes.c_uint32])
 register('savp_debug_probe_lds', [c_vp, ctypes.c_uint32, c_vp])

@@ -158,9 +158,11 @@ class ConcatNorm(object):
 
 
 class SAVPGenerator(object):
-    def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0)):
+    def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0), pix=0):
         """cond = (n_actions, n_states): widths of inputs['actions'] / inputs['states'] (savp_model.py:411-444): [actions_t | state_t]
-        joins the latent in every tile-concatenated slice, the next state is predicted by `state_pred/dense` (:655-658)."""
+        joins the latent in every tile-concatenated slice, the next state is predicted by `state_pred/dense` (:655-658).
+        pix = P: designated pixels of inputs['pix_distribs'] (:408-410,598-621,648-653); 0 = the model has no such input and nothing below
+        allocates or launches anything for it."""
         H, W, C = image_shape
         self.hp, self.store, self.N, self.H, self.W, self.C = hp, store, N, H, W, C
         self._ones = None
@@ -549,6 +551,16 @@ class SAVPGenerator(object):
                      [L['cconv'] for L in self.layers if L['rnn'] and self.gru and not self.abl_rnn] + \
                      ([self.fc_z] if (self.use_rnn_z and self.abl_rnn) else []) + \
                      tf_convs + head_convs + ([self.scratch_out] if self.scratch else []) + [self.masks_out]
+        # ---- pix_distribs: one launch after the unroll (pix_distribs_forward); the slots in the reference's order (:598-621) ----
+        self.P = int(pix)
+        if self.P:
+            kinds = {'prev': lib.PIX_SLOT_CURRENT, 'fixed': lib.PIX_SLOT_FIXED, 'last_context': lib.PIX_SLOT_LAST_CONTEXT}
+            self.pix_slots = [(lib.PIX_SLOT_TRANSFORMED, m) for m in range(nk)] + \
+                             [(kinds[bg[0]], bg[1] if bg[0] == 'fixed' else 0) for bg in self.bgs] + \
+                             ([(lib.PIX_SLOT_CURRENT, 0)] if self.scratch else [])          # :620-621: the scratch slot takes pix_distrib again
+            assert len(self.pix_slots) == M
+            self.gen_pix = torch.empty(T1, N, H, W, self.P, device=dev)
+            self.tr_pix = None                   # [T1, N, H, W, P, M], allocated when first asked for
         # only FPROP packs needed at inference
         self._routes()
 
@@ -814,6 +826,19 @@ class SAVPGenerator(object):
             K.composite_fwd(self.logits.v[t], maskin.v[t][..., self.hp.ngf:self.hp.ngf + self.M * C], self.gen.v[t],
                             self.masks[t] if collect_masks else None, M=self.M, next_inputs=nxt)
         return self.gen.v
+
+    def pix_distribs_forward(self, pix_in, transformed=False):
+        """gen_pix_distribs (and transformed_pix_distribs) of the unroll forward() has just run: pix_in [>= T1, N, H, W, P] time-major, the
+        scheduled-sampling mask, kernels / flows and mask logits are the unroll's own.  One launch (csrc/pix_distribs.hip), never part of a
+        train step or a captured sequence.  Returns gen_pix [T1, N, H, W, P] (a buffer of the generator)."""
+        if not self.P:
+            raise RuntimeError('this generator was built without pix_distribs (pix=0)')
+        if transformed and self.tr_pix is None:
+            self.tr_pix = torch.empty(self.T1, self.N, self.H, self.W, self.P, self.M, device=self.dev)
+        tfp = self.cdna_kern.v if self.tf == 'cdna' else (self.dna_kern if self.tf == 'dna' else self.tf_raw.v)
+        K.pix_distribs_fwd(pix_in, self.gt_mask, self.tf, tfp, self.logits.v, self.gen_pix, self.pix_slots, self.L, self.nti,
+                           self.hp.context_frames, self.kh, self.kw, transformed=self.tr_pix if transformed else None)
+        return self.gen_pix
 
     def _norm(self, scope, c, kind=None, bias=None):
         """The normalizer_fn of `kind` (default: norm_layer) under `scope`: <scope>InstanceNorm/ or <scope>LayerNorm/; bias: the variable

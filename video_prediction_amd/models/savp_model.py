@@ -127,8 +127,10 @@ class SAVPEngine(object):
     UNSUPPORTED_WEIGHTS = ('vgg_cdist_weight', 'feature_l2_weight', 'ae_l2_weight')
 
     def __init__(self, hp, image_shape, batch_size, mode='train', values=None, seed=4, device='cuda:0', base_seed=0, rank=0,
-                 cond=(0, 0), lpips_weights=None):
-        """cond = (n_actions, n_states): the widths of inputs['actions'] [B, T-1, na] / inputs['states'] [B, T, ns] when the dataset
+                 cond=(0, 0), lpips_weights=None, pix_distribs=0):
+        """pix_distribs = P: the number of designated pixels of inputs['pix_distribs'] [B, T, H, W, P] (savp_model.py:252-255,408-410,598-621,
+        648-653); 0 (the default) = a model without that input: the key is refused and no buffer, launch or graph node exists for it.
+        cond = (n_actions, n_states): the widths of inputs['actions'] [B, T-1, na] / inputs['states'] [B, T, ns] when the dataset
         supplies them (the action / state-conditioned model, savp_model.py:24-26,411-444,655-661; base_model.py:758-762).
         lpips_weights: path of the LPIPS network's .npz (video_prediction_amd.lpips; default: the SAVP_LPIPS_WEIGHTS environment
         variable); without one the lpips metric and eval_diversity are not produced."""
@@ -155,7 +157,13 @@ class SAVPEngine(object):
         self.T, self.T1 = hp.sequence_length, hp.sequence_length - 1
         H, W, C = image_shape
         self.N = N = 2 * B if self.nz else B
-        self.gen = SAVPGenerator(self.store, hp, image_shape, N, train=self.train, cond=self.cond)
+        self.P = int(pix_distribs or 0)
+        if self.P < 0:
+            raise ValueError('pix_distribs = %r: the number of designated pixels' % (pix_distribs,))
+        self.gen = SAVPGenerator(self.store, hp, image_shape, N, train=self.train, cond=self.cond, pix=self.P)
+        # designated-pixel distributions, staged time-major beside the images (sliced to T1 like every input: savp_model.py:690-691)
+        self.pix_tm = torch.empty(self.T1, B, H, W, self.P, device=self.device) if self.P else None
+        self.pix_n = (torch.empty(self.T1, N, H, W, self.P, device=self.device) if self.nz else self.pix_tm) if self.P else None
         self.enc = PosteriorEncoder(self.store, hp, image_shape, B, train=self.train, n_actions=self.na) if self.nz else None
         # conditioning inputs, time-major; both unrolls (N = 2B: posterior half, prior half) see the same actions / states
         self.actions_tm = torch.zeros(self.T1, B, self.na, device=self.device) if self.na else None
@@ -320,12 +328,50 @@ class SAVPEngine(object):
                 buf_n[:, :self.B].copy_(buf)
                 buf_n[:, self.B:].copy_(buf)
 
+    def set_pix_distribs(self, pix, time_major=False):
+        """pix [B, T, H, W, P] (reference layout; [T, B, ...] if time_major) with T >= T1, sliced to T1 (tf_utils.maybe_pad_or_slice)."""
+        if not self.P:
+            raise ValueError("inputs['pix_distribs'] given to a model built without it (build_graph fixes the input structure)")
+        if pix is None:
+            raise KeyError('pix_distribs')
+        pix = torch.as_tensor(pix)
+        pix = pix if time_major else pix.transpose(0, 1)
+        if pix.dim() != 5 or pix.shape[0] < self.T1 or tuple(pix.shape[1:]) != tuple(self.pix_tm.shape[1:]):
+            raise ValueError("inputs['pix_distribs']: expected >= %d steps of %r, got %r"
+                             % (self.T1, tuple(self.pix_tm.shape[1:]), tuple(pix.shape)))
+        self.pix_tm.copy_(pix[:self.T1])
+        if self.pix_n is not self.pix_tm:
+            self.pix_n[:, :self.B].copy_(self.pix_tm)
+            self.pix_n[:, self.B:].copy_(self.pix_tm)
+
+    def pix_distribs_pass(self, transformed=False):
+        """gen_pix_distribs (and transformed_pix_distribs) of the unroll that has just run, both halves of the N = 2B batch: one eager
+        launch behind the unroll, never inside a train step or a captured sequence."""
+        return self.gen.pix_distribs_forward(self.pix_n, transformed=transformed)
+
+    def pix_views(self):
+        """The pixel-distribution outputs of the last pass with the reference's keys (savp_model.py:663-665): gen_pix_distribs
+        [T1, B, H, W, P], transformed_pix_distribs [.., P, M] when the pass produced them, and their '_enc' twins (the posterior half)."""
+        g, B = self.gen, self.B
+        both = OrderedDict([('gen_pix_distribs', g.gen_pix)])
+        if g.tr_pix is not None:
+            both['transformed_pix_distribs'] = g.tr_pix
+        lo = B if self.nz else 0
+        out = OrderedDict((k, v[:, lo:]) for k, v in both.items())
+        if self.nz:
+            out.update((k + '_enc', v[:, :B]) for k, v in both.items())
+        return out
+
     def set_images(self, images, time_major=False):
         """images: device fp32 [B,T,H,W,C] (reference layout) or [T,B,H,W,C] if time_major; or the dataset's inputs dict ('images' and,
-        for a model built with cond, 'actions' / 'states'; 'pix_distribs' is refused, see refuse_conditioning_inputs)."""
+        for a model built with cond, 'actions' / 'states'; 'pix_distribs' for an engine built with pix_distribs = P > 0, refused by every
+        other, see refuse_conditioning_inputs)."""
         if isinstance(images, dict):
-            refuse_conditioning_inputs(images)
+            if not getattr(self, 'P', 0):
+                refuse_conditioning_inputs(images)
             self.set_conditioning(images.get('actions'), images.get('states'), time_major=time_major)
+            if getattr(self, 'P', 0):
+                self.set_pix_distribs(images.get('pix_distribs'), time_major=time_major)
             images = images['images']
         T = self.T
         if time_major:
@@ -457,6 +503,8 @@ class SAVPEngine(object):
             gen = self.gen.forward(self.images_n, None, gt, collect_masks=collect_masks, actions=self.actions_n, states=self.states_n)
         if collect_masks and hp.transformation == 'flow':
             self._flows_to_rgb()
+        if collect_masks and self.P:               # generator_fn and the image summary: every output of the cell, these included
+            self.pix_distribs_pass(transformed=True)
         return gen
 
     def _flows_to_rgb(self):
@@ -751,6 +799,14 @@ class SAVPEngine(object):
 
     # -- inference (scripts/generate.py:166: model.outputs['gen_images']) ------------------------------------------------------
     def generate(self, noise=None, collect_masks=False):
+        """_unroll, then -- for an engine built with pix_distribs -- the pixel-distribution pass on the unroll's buffers (eager, one launch;
+        with collect_masks forward_generator has already run it)."""
+        gen = self._unroll(noise, collect_masks)
+        if self.P and not collect_masks:
+            self.pix_distribs_pass()
+        return gen
+
+    def _unroll(self, noise=None, collect_masks=False):
         """One prior (and posterior) unroll of the generator on the staged images: gen [T1, N, H, W, C] (a buffer of the engine: the
         next call overwrites it).  Like the train step, the launch sequence (weight preparation + unroll, ~1 k launches) has no host
         input once the noise is staged, so from the second call on it is replayed as ONE hipGraph (SAVP_INFER_GRAPH=0: eager): the
@@ -1131,8 +1187,15 @@ def cond_of(inputs):
     return (int(a.shape[-1]) if a is not None else 0, int(s_.shape[-1]) if s_ is not None else 0)
 
 
+def pix_distribs_opt_in(flag=None):
+    """The opt-in of the pixel-distribution outputs: the keyword where one was given, else SAVP_PIX_DISTRIBS=1 in the environment (for callers
+    that build classes with the reference's signatures).  Without it nothing changes: inputs['pix_distribs'] is refused."""
+    return bool(flag) if flag is not None else os.environ.get('SAVP_PIX_DISTRIBS', '0') == '1'
+
+
 def _engine_for(inputs, mode, hparams, engine=None):
-    refuse_conditioning_inputs(inputs)
+    if not getattr(engine, 'P', 0):                # only an engine built with pix_distribs = P > 0 takes the key
+        refuse_conditioning_inputs(inputs)
     images = inputs['images']
     if engine is not None:
         return engine
@@ -1200,6 +1263,8 @@ def generator_fn(inputs, mode, hparams, engine=None, noise=None, samples=False):
     outputs['ground_truth_sampling_mean'] = gt[hparams.context_frames:, lo:].float().mean()
     if eng.ns:
         outputs['gen_states'] = g.gen_states.v[:, lo:]             # savp_model.py:666-667
+    pix = eng.pix_views() if eng.P else {}                         # savp_model.py:663-665
+    outputs.update((k, v) for k, v in pix.items() if not k.endswith('_enc'))
     if eng.learn_prior:
         outputs['zs_mu_prior'] = eng.prior.mu                    # savp_model.py:735 (keys get the '_prior' suffix)
         outputs['zs_log_sigma_sq_prior'] = eng.prior.ls
@@ -1215,6 +1280,7 @@ def generator_fn(inputs, mode, hparams, engine=None, noise=None, samples=False):
         outputs['ground_truth_sampling_mean_enc'] = gt[hparams.context_frames:, :B].float().mean()
         if eng.ns:
             outputs['gen_states_enc'] = g.gen_states.v[:, :B]
+        outputs.update((k, v) for k, v in pix.items() if k.endswith('_enc'))
     if eng.nz and (samples or 'samples_prior' in noise or 'samples_prior_eps' in noise):
         # the prior half of one more 2B unroll per draw (the posterior half repeats the posterior unroll above: same eps, same schedule)
         key = 'samples_prior_eps' if eng.learn_prior else 'samples_prior'
@@ -1272,6 +1338,8 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
     def __init__(self, *args, **kwargs):
         # path of the LPIPS network's weights (video_prediction_amd.lpips); None: the SAVP_LPIPS_WEIGHTS environment variable, if set
         self.lpips_weights = kwargs.pop('lpips_weights', None)
+        # opt-in of the designated-pixel distribution outputs (pix_distribs=True, or SAVP_PIX_DISTRIBS=1); without it the key is refused
+        self.pix_distribs = pix_distribs_opt_in(kwargs.pop('pix_distribs', None))
         super(SAVPVideoPredictionModel, self).__init__(generator_fn, discriminator_fn, *args, **kwargs)
         if self.mode != 'train':
             self.discriminator_fn = None
@@ -1290,13 +1358,18 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
     def build_graph(self, inputs, values=None, seed=4, device='cuda:0'):
         """inputs: {'images': [B,T,H,W,C] device tensor, optionally 'actions': [B,T-1,na], 'states': [B,T,ns]} (batch-major like the
         reference's dataset iterator).  As in the reference the input STRUCTURE is fixed here: a model built with actions / states
-        expects them in every later batch."""
-        refuse_conditioning_inputs(inputs)
+        expects them in every later batch.  A model created with the pix_distribs opt-in also reads P off inputs['pix_distribs']
+        [B,T,H,W,P] when the batch carries it; every other model refuses the key."""
+        P = 0
+        if self.pix_distribs and isinstance(inputs, dict) and inputs.get('pix_distribs') is not None:
+            P = int(inputs['pix_distribs'].shape[-1])
+        else:
+            refuse_conditioning_inputs(inputs)
         super(SAVPVideoPredictionModel, self).build_graph(inputs)
         images = inputs['images']
         B = images.shape[0]
         self.engine = SAVPEngine(self.hparams, tuple(images.shape[2:]), B, mode=self.mode, values=values, seed=seed,
-                                 device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights)
+                                 device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights, pix_distribs=P)
         self.saveable_variables = self.engine.store.names()
         self.post_init_ops = []
         self.outputs = {}
@@ -1306,10 +1379,15 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
     def global_step(self):
         return self.engine.step if self.engine else 0
 
-    def train_step(self, inputs=None, noise=None):
-        """One ``sess.run(model.train_op)``."""
-        if inputs is not None:
+    def _refuse(self, inputs):
+        """refuse_conditioning_inputs unless this model's engine was built for pix_distribs (the engine then checks every batch itself)."""
+        if not getattr(self.engine, 'P', 0):
             refuse_conditioning_inputs(inputs)
+
+    def train_step(self, inputs=None, noise=None):
+        """One ``sess.run(model.train_op)`` (the pixel-distribution pass is not part of it: nothing in a train step reads it)."""
+        if inputs is not None:
+            self._refuse(inputs)
             self.inputs = inputs
         self.engine.set_images(self.inputs)
         info = self.engine.train_step(noise)
@@ -1318,9 +1396,10 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         return info
 
     def generate(self, inputs=None, noise=None):
-        """Fills self.outputs['gen_images'] batch-major [B,T-1,H,W,C] (scripts/generate.py:166)."""
+        """Fills self.outputs['gen_images'] batch-major [B,T-1,H,W,C] (scripts/generate.py:166) and, for a model built with pix_distribs,
+        'gen_pix_distribs' [B,T-1,H,W,P]; with a latent also their '_enc' twins."""
         if inputs is not None:
-            refuse_conditioning_inputs(inputs)
+            self._refuse(inputs)
             self.inputs = inputs
         self.engine.set_images(self.inputs)
         gen = self.engine.generate(noise)
@@ -1328,6 +1407,10 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         self.outputs['gen_images'] = gen[:, lo:].transpose(0, 1)
         if self.engine.nz:
             self.outputs['gen_images_enc'] = gen[:, :self.engine.B].transpose(0, 1)
+        if self.engine.P:
+            for k, v in self.engine.pix_views().items():
+                if k.startswith('gen_pix_distribs'):
+                    self.outputs[k] = v.transpose(0, 1)
         return self.outputs
 
     def metrics_fn(self, inputs=None, outputs=None):
@@ -1362,7 +1445,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
 
     def _stage(self, inputs):
         if inputs is not None:
-            refuse_conditioning_inputs(inputs)
+            self._refuse(inputs)
             self.inputs = inputs
         self.engine.set_images(self.inputs)
 
