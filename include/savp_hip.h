@@ -373,6 +373,9 @@ int savp_adam(void* stream, int64_t n, float* p, const float* g, float* m, float
 int savp_cdna_kernels_fwd(void* stream, const float* raw, float* kern, int32_t N, int32_t kh, int32_t kw, int32_t K);
 int savp_cdna_kernels_bwd(void* stream, const float* raw, const double* dkern, float* draw, int32_t N, int32_t kh, int32_t kw,
                           int32_t K);
+/* Any kernel size of 1 .. 49 taps (CDNA; DNA has no tap limit).  The image is SYMMETRIC-padded like tf.pad under 'SAME': (k-1)/2 before,
+ * the rest after, and like tf.pad a pad larger than the image is refused: max(pad before, pad after) > H (or W) and kh, kw < 1 are
+ * SAVP_EINVAL in every CDNA / DNA apply entry, single- and multi-source, and in savp_pix_distribs_fwd. */
 typedef struct SavpCdnaArgs {
     int32_t N, H, W, C, K, kh, kw;
     SavpView img;                  /* [N,H,W,C] */

@@ -117,13 +117,14 @@ def check_generator_forward(nz=0, B=2, T=5, H=64, W=64, C=3, seed=0, tag=None, c
     mism = (masks[:, lo:].squeeze(-2).argmax(-1).cpu() != m_ref.argmax(-1)) & safe
     out.append((tag + '/mask_argmax_mismatch_frac', float(mism.sum()) / float(safe.sum()), 0.0))
     if hp.transformation == 'cdna':
-        kern_ref = ref['_kernels']                                   # [T1,B,5,5,4]
-        kern = g.cdna_kern.v.reshape(g.T1, g.N, 5, 5, 4)[:, lo:]
+        kh, kw = hp.kernel_size
+        kern_ref = ref['_kernels']                                   # [T1,B,kh,kw,4]
+        kern = g.cdna_kern.v.reshape(g.T1, g.N, kh, kw, 4)[:, lo:]
         out.append((tag + '/cdna_kernels', rel(kern, kern_ref), 1e-3))
-        kr = kern_ref.reshape(g.T1, B, 25, 4)
+        kr = kern_ref.reshape(g.T1, B, kh * kw, 4)
         t2 = kr.topk(2, dim=2).values
         safe = (t2[:, :, 0] - t2[:, :, 1]) > 1e-5
-        mism = (kern.reshape(g.T1, B, 25, 4).argmax(2).cpu() != kr.argmax(2)) & safe
+        mism = (kern.reshape(g.T1, B, kh * kw, 4).argmax(2).cpu() != kr.argmax(2)) & safe
         out.append((tag + '/cdna_tap_argmax_mismatch', float(mism.sum()), 0.0))
     if nz:
         out.append((tag + '/gen_images_enc', rel(gen[:, :B], ref['gen_images_enc']), 1e-3))

@@ -72,31 +72,31 @@ def _ref(tf, imgs, params, dout, L, nti, kh=5, kw=5):
     return out.detach(), [x.grad for x in imgs64], p64.grad
 
 
-def _params(tf, nk, seed):
+def _params(tf, nk, seed, kh=5, kw=5):
     g = torch.Generator().manual_seed(seed)
-    if tf == 'cdna':                      # normalised kernels [N, 25, nk]
-        k = torch.rand(N, 25, nk, generator=g) + 0.05
+    if tf == 'cdna':                      # normalised kernels [N, kh * kw, nk]
+        k = torch.rand(N, kh * kw, nk, generator=g) + 0.05
         return (k / k.sum(dim=1, keepdim=True)).to(DEV)
-    if tf == 'dna':                       # raw conv output [N, H, W, 25 * nk]
-        return (0.3 * torch.randn(N, H, W, 25 * nk, generator=g)).to(DEV)
+    if tf == 'dna':                       # raw conv output [N, H, W, kh * kw * nk]
+        return (0.3 * torch.randn(N, H, W, kh * kw * nk, generator=g)).to(DEV)
     return (2.5 * torch.randn(N, H, W, 2 * nk, generator=g)).to(DEV)          # flows, x components then y
 
 
-def _run(tf, imgs, params, out, dout, dimgs, betas, nti):
+def _run(tf, imgs, params, out, dout, dimgs, betas, nti, kh=5, kw=5):
     """The multi-source entry: forward into out, backward with the given gradient destinations.  Returns the parameter gradient."""
     from video_prediction_amd import kernels as K
     L = len(imgs)
     nk = L * nti
     if tf == 'cdna':
-        K.cdna_apply_multi_fwd(imgs, params, out, 5, 5, nti)
-        dk = torch.empty(N, 25, nk, device=DEV, dtype=torch.float64)
-        K.cdna_apply_multi_bwd(imgs, params, dout, dimgs, dk, 5, 5, nti, betas)
+        K.cdna_apply_multi_fwd(imgs, params, out, kh, kw, nti)
+        dk = torch.empty(N, kh * kw, nk, device=DEV, dtype=torch.float64)
+        K.cdna_apply_multi_bwd(imgs, params, dout, dimgs, dk, kh, kw, nti, betas)
         return dk
     if tf == 'dna':
         kern = torch.empty_like(params)
-        K.dna_apply_multi_fwd(imgs, params, kern, out, 5, 5, nti)
+        K.dna_apply_multi_fwd(imgs, params, kern, out, kh, kw, nti)
         draw = torch.empty_like(params)
-        K.dna_apply_multi_bwd(imgs, params, kern, dout, draw, dimgs, 5, 5, nti, betas)
+        K.dna_apply_multi_bwd(imgs, params, kern, dout, draw, dimgs, kh, kw, nti, betas)
         return draw
     K.image_warp_multi_fwd(imgs, params, out, nti)
     dfl = torch.empty_like(params)
@@ -104,17 +104,22 @@ def _run(tf, imgs, params, out, dout, dimgs, betas, nti):
     return dfl
 
 
-@pytest.mark.parametrize('L', [1, 2, 3])
-@pytest.mark.parametrize('C', [1, 3])
-@pytest.mark.parametrize('tf,nti', [('cdna', 4), ('cdna', 3), ('dna', 2), ('flow', 2)])
-def test_multi_source_transformations_vs_fp64(tf, nti, C, L):
+_TF_NTI = [('cdna', 4), ('cdna', 3), ('dna', 2), ('flow', 2)]
+# every transformation at 5 x 5 over L x C, then the general (any-size) kernels at an odd and an even size, L = 2, C = 3
+_MULTI = [pytest.param(tf, nti, C, L, 5, 5, id='%s-%d-%d-%d' % (tf, nti, C, L)) for L in (1, 2, 3) for C in (1, 3) for tf, nti in _TF_NTI] + \
+         [pytest.param(tf, nti, 3, 2, kh, kw, id='%s-%d-3-2-k%dx%d' % (tf, nti, kh, kw))
+          for kh, kw in ((3, 3), (4, 4)) for tf, nti in _TF_NTI[:3]]
+
+
+@pytest.mark.parametrize('tf,nti,C,L,kh,kw', _MULTI)
+def test_multi_source_transformations_vs_fp64(tf, nti, C, L, kh, kw):
     """Forward and backward of the multi-source entries on strided views against fp64: every source's image gradient (overwritten for
     some, accumulated onto what the destination held for others, not wanted for one when L > 1) and the gradient of all L * nti kernel /
-    flow columns.  cdna nti = 4 runs the LDS-tiled kernels, nti = 3 the general ones."""
+    flow columns.  cdna nti = 4 runs the LDS-tiled kernels at 5 x 5, nti = 3 and every other kernel size the general ones."""
     nk = L * nti
     seed = 100 * L + 10 * C + nti
     imgs = _sources(L, C, seed)
-    params = _params(tf, nk, seed + 1)
+    params = _params(tf, nk, seed + 1, kh, kw)
     out = _slot(nk, C, seed + 2)
     dout = _slot(nk, C, seed + 3)
     row_before = out._base.clone() if out._base is not None else None
@@ -123,9 +128,9 @@ def test_multi_source_transformations_vs_fp64(tf, nti, C, L):
     prior = dbuf.clone()
     dimgs = [None if (L > 1 and j == 0) else dbuf[j][..., 1:1 + C] for j in range(L)]
     betas = [j % 2 for j in range(L)]
-    dpar = _run(tf, imgs, params, out, dout, dimgs, betas, nti)
+    dpar = _run(tf, imgs, params, out, dout, dimgs, betas, nti, kh, kw)
     torch.cuda.synchronize()
-    ref_out, ref_dimgs, ref_dpar = _ref(tf, imgs, params, dout, L, nti)
+    ref_out, ref_dimgs, ref_dpar = _ref(tf, imgs, params, dout, L, nti, kh, kw)
     res = [('out', _rel(out, ref_out), 1e-5), ('dparams', _rel(dpar, ref_dpar.reshape(dpar.shape)), 1e-4)]
     for j in range(L):
         if dimgs[j] is None:
@@ -246,7 +251,7 @@ def _generator_forward(transformation, L, nz=8, B=2, T=7, Hm=64, Wm=64, C=3, see
     out.append((tag + '/transformed_images', G.rel(eng.gen.maskin.v[:, lo:, ..., hp.ngf:hp.ngf + g.nk * C].reshape(g.T1, B, Hm, Wm, g.nk, C)
                                                    .transpose(-1, -2), ref['transformed_images'][..., :g.nk]), 1e-3))
     if transformation == 'cdna':
-        kern = g.cdna_kern.v.reshape(g.T1, g.N, 5, 5, g.nk)[:, lo:]
+        kern = g.cdna_kern.v.reshape(g.T1, g.N, hp.kernel_size[0], hp.kernel_size[1], g.nk)[:, lo:]
         out.append((tag + '/cdna_kernels', G.rel(kern, ref['_kernels']), 1e-3))
     if nz:
         out.append((tag + '/gen_images_enc', G.rel(gen[:, :B], ref['gen_images_enc']), 1e-3))

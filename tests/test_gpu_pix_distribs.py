@@ -46,11 +46,11 @@ def _gt_rows(n=N):
     return torch.tensor([r[:n] for r in rows], dtype=torch.int32)
 
 
-def _case_inputs(tf, L, nti, H, W, P, seed, n=N, strided=True):
+def _case_inputs(tf, L, nti, H, W, P, seed, n=N, strided=True, ks=(5, 5)):
     """fp32 inputs on the device as the unroll keeps them: pix_in as a channel slice of a wider buffer, logits in a row padded to a
     multiple of four, flows in a padded row; random positive kernels, flows and logits."""
     g = torch.Generator().manual_seed(seed)
-    nk = L * nti
+    nk, taps = L * nti, ks[0] * ks[1]
     pix = torch.rand(T1 + 1, n, H, W, P, generator=g) + 0.01
     pix = pix / pix.sum(dim=(2, 3), keepdim=True)
     if strided:
@@ -60,11 +60,11 @@ def _case_inputs(tf, L, nti, H, W, P, seed, n=N, strided=True):
     else:
         pix_dev = pix.to(DEV)
     if tf == 'cdna':
-        k = torch.rand(T1, n, 25, nk, generator=g) + 0.02
+        k = torch.rand(T1, n, taps, nk, generator=g) + 0.02
         tfp = k / k.sum(dim=2, keepdim=True)
     elif tf == 'dna':
-        k = torch.rand(T1, n, H, W, 25, nk, generator=g) + 0.02
-        tfp = (k / k.sum(dim=4, keepdim=True)).reshape(T1, n, H, W, 25 * nk)
+        k = torch.rand(T1, n, H, W, taps, nk, generator=g) + 0.02
+        tfp = (k / k.sum(dim=4, keepdim=True)).reshape(T1, n, H, W, taps * nk)
     else:
         tfp = torch.zeros(T1, n, H, W, (2 * nk + 3) // 4 * 4)
         tfp[..., :2 * nk] = 2.0 * torch.randn(T1, n, H, W, 2 * nk, generator=g)
@@ -77,10 +77,11 @@ def _oracle(hp, pix_dev, gt, tfp, masks64, H, W):
     pix64 = pix_dev.detach().double().cpu()
     t64 = tfp.detach().double().cpu()
     kernels = flows = None
+    kh, kw = hp.kernel_size
     if hp.transformation == 'cdna':
-        kernels = t64.reshape(T1, n, 5, 5, nk)
+        kernels = t64.reshape(T1, n, kh, kw, nk)
     elif hp.transformation == 'dna':
-        kernels = t64.reshape(T1, n, H, W, 5, 5, nk)
+        kernels = t64.reshape(T1, n, H, W, kh, kw, nk)
     else:
         flows = t64[..., :2 * nk].reshape(T1, n, H, W, 2, nk)
     return OP.recurrence(pix64, gt.bool(), hp, masks64, kernels=kernels, flows=flows)
@@ -93,17 +94,17 @@ def _map_err(got, ref):
     return float((num / ref.amax(dim=(2, 3))).max())
 
 
-def _a_priori(tf, nk, M, H, W):
-    taps = 4 if tf == 'flow' else 25
+def _a_priori(tf, nk, M, H, W, ks=(5, 5)):
+    taps = 4 if tf == 'flow' else ks[0] * ks[1]
     return (nk * taps + M + math.log2(H * W) + 4) * T1 * 2.0 ** -24
 
 
-def _run_case(tf, L, nti, H, W, P, bg, transformed, force_global, seed, expect_resident=None):
+def _run_case(tf, L, nti, H, W, P, bg, transformed, force_global, seed, expect_resident=None, ks=(5, 5)):
     from video_prediction_amd import kernels as K
-    hp = _hp(tf, L, nti, **bg)
+    hp = _hp(tf, L, nti, kernel_size=ks, **bg)
     names = OP.slot_names(hp)
     M, nk = len(names), L * nti
-    pix_dev, tfp, g = _case_inputs(tf, L, nti, H, W, P, seed)
+    pix_dev, tfp, g = _case_inputs(tf, L, nti, H, W, P, seed, ks=ks)
     logits = torch.zeros(T1, N, H, W, (M + 3) // 4 * 4)
     logits[..., :M] = 2.0 * torch.randn(T1, N, H, W, M, generator=g)
     logits = logits.to(DEV)
@@ -114,18 +115,18 @@ def _run_case(tf, L, nti, H, W, P, bg, transformed, force_global, seed, expect_r
     slots = [(kinds[k], a) for k, a in names]
     gen = torch.empty(T1, N, H, W, P, device=DEV)
     tr = torch.empty(T1, N, H, W, P, M, device=DEV) if transformed else None
-    resident = K.pix_distribs_fwd(pix_dev, gt, tf, tfp, logits, gen, slots, L, nti, CF, 5, 5, transformed=tr, force_global=force_global)
+    resident = K.pix_distribs_fwd(pix_dev, gt, tf, tfp, logits, gen, slots, L, nti, CF, ks[0], ks[1], transformed=tr, force_global=force_global)
     gen2 = torch.empty_like(gen)
-    K.pix_distribs_fwd(pix_dev, gt, tf, tfp, logits, gen2, slots, L, nti, CF, 5, 5, force_global=force_global)
+    K.pix_distribs_fwd(pix_dev, gt, tf, tfp, logits, gen2, slots, L, nti, CF, ks[0], ks[1], force_global=force_global)
     torch.cuda.synchronize()
     assert resident == (not force_global if expect_resident is None else expect_resident)
     masks64 = torch.softmax(logits[..., :M].double().cpu(), dim=-1)
     ref_gen, ref_tr = _oracle(hp, pix_dev, gt.cpu(), tfp, masks64, H, W)
     err = _map_err(gen, ref_gen)
-    bound = _a_priori(tf, nk, M, H, W)
+    bound = _a_priori(tf, nk, M, H, W, ks)
     sums = gen.double().sum(dim=(2, 3))
-    print('pix_distribs op %s L=%d nti=%d %dx%d P=%d M=%d %s: err %.3e  a-priori %.3e  gate %.3e  max |sum - 1| %.3e'
-          % (tf, L, nti, H, W, P, M, 'lds' if resident else 'global', err, bound, OP_GATE, float((sums - 1).abs().max())))
+    print('pix_distribs op %s k%dx%d L=%d nti=%d %dx%d P=%d M=%d %s: err %.3e  a-priori %.3e  gate %.3e  max |sum - 1| %.3e'
+          % (tf, ks[0], ks[1], L, nti, H, W, P, M, 'lds' if resident else 'global', err, bound, OP_GATE, float((sums - 1).abs().max())))
     assert torch.equal(_bits(gen), _bits(gen2)), 'two launches differ'
     assert float((sums - 1).abs().max()) <= 1e-5
     if transformed:
@@ -146,6 +147,16 @@ def test_recurrence_vs_float64(i):
     tf, L, (H, W) = _GRID[i]
     _run_case(tf, L, 4 if L == 1 else 2, H, W, P=(1, 3)[(i + i // 2) % 2], bg=BACKGROUNDS[i % len(BACKGROUNDS)],
               transformed=(i + i // 4) % 2 == 1, force_global=i % 3 == 0, seed=40 + i)
+
+
+_SIZES = [(tf, ks, fg) for tf in ('cdna', 'dna') for ks in ((3, 3), (4, 4)) for fg in (False, True)]
+
+
+@pytest.mark.parametrize('tf,ks,force_global', _SIZES, ids=['%s-k%dx%d-%s' % (tf, ks[0], ks[1], 'global' if fg else 'lds') for tf, ks, fg in _SIZES])
+def test_recurrence_at_another_kernel_size_vs_float64(tf, ks, force_global):
+    """kernel_size (3, 3) and (4, 4) on 8 x 8: the any-window loop of the kernel (the unrolled one is 5 x 5 only), an even size with its
+    unequal pads, sources in LDS and in global memory.  Same gate and a-priori bound (with the window's own tap count) as at 5 x 5."""
+    _run_case(tf, 2, 2, 8, 8, P=3, bg=BACKGROUNDS[0], transformed=True, force_global=force_global, seed=70 + ks[0], ks=ks)
 
 
 def test_recurrence_64x64_with_four_sources_is_lds_resident():

@@ -59,7 +59,8 @@ __global__ __launch_bounds__(CK_NT) void cdna_kernels_fwd_kernel(const float* __
         v = fmaxf(raw[base + e] + ident_at(t / kw, t % kw, kh, kw) - RELU_SHIFT, 0.f) + RELU_SHIFT;
     }
     const float s = cdna_tap_sum(sh, v, e, taps, K, live);
-    if (live) kern[base + e] = v * (1.f / s);
+    // a lone tap (1 x 1) is its own sum: k / k is exactly 1 in the reference, which v * (1 / v) in float32 is not for one value in eight
+    if (live) kern[base + e] = taps == 1 ? 1.f : v * (1.f / s);
 }
 
 // draw = ((dkern - sum(dkern*kern)) / s) * [raw + ident - shift > 0]
@@ -79,17 +80,17 @@ __global__ __launch_bounds__(CK_NT) void cdna_kernels_bwd_kernel(const float* __
     const float s = cdna_tap_sum(sh, v, e, taps, K, live);
     const float inv = live ? 1.f / s : 0.f;
     const float dot = cdna_tap_sum(sh, d * v * inv, e, taps, K, live);
-    if (live) draw[base + e] = pre > 0.f ? (d - dot) * inv : 0.f;
+    if (live) draw[base + e] = (pre > 0.f && taps > 1) ? (d - dot) * inv : 0.f;       // a lone tap: d(k / k) = 0 exactly
 }
 
 extern "C" int savp_cdna_kernels_fwd(void* stream, const float* raw, float* kern, int32_t N, int32_t kh, int32_t kw, int32_t K) {
-    if (!raw || !kern || N < 1 || kh * kw * K > CK_NT) return SAVP_EINVAL;
+    if (!raw || !kern || N < 1 || kh < 1 || kw < 1 || K < 1 || kh * kw * K > CK_NT) return SAVP_EINVAL;
     hipLaunchKernelGGL(cdna_kernels_fwd_kernel, dim3(N), dim3(CK_NT), 0, (hipStream_t)stream, raw, kern, kh, kw, K);
     return LAUNCH_OK();
 }
 extern "C" int savp_cdna_kernels_bwd(void* stream, const float* raw, const double* dkern, float* draw, int32_t N, int32_t kh,
                                      int32_t kw, int32_t K) {
-    if (!raw || !dkern || !draw || N < 1 || kh * kw * K > CK_NT) return SAVP_EINVAL;
+    if (!raw || !dkern || !draw || N < 1 || kh < 1 || kw < 1 || K < 1 || kh * kw * K > CK_NT) return SAVP_EINVAL;
     hipLaunchKernelGGL(cdna_kernels_bwd_kernel, dim3(N), dim3(CK_NT), 0, (hipStream_t)stream, raw, dkern, draw, kh, kw, K);
     return LAUNCH_OK();
 }
@@ -644,8 +645,16 @@ __global__ __launch_bounds__(NT) void cdna_bwd_kern_tiled_kernel(CdnaP p, int ti
     }
 }
 
+// tf.pad SYMMETRIC takes a pad of at most the image's size (sym() mirrors once): the SAME pads before / after are (k-1)/2 and the rest
+static bool cdna_pad_fits(int kh, int kw, int H, int W) {
+    if (kh < 1 || kw < 1) return false;
+    const int pt = (kh - 1) / 2, pl = (kw - 1) / 2;
+    return max(pt, kh - 1 - pt) <= H && max(pl, kw - 1 - pl) <= W;
+}
+
 static int fill_cdna(CdnaP& p, const SavpCdnaArgs* a) {
     if (!a || a->kh * a->kw > MAXTAPS || a->K > MAXK || a->C > MAXC || a->K < 1 || a->C < 1) return SAVP_EINVAL;
+    if (!cdna_pad_fits(a->kh, a->kw, a->H, a->W)) return SAVP_EINVAL;
     p.N = a->N; p.H = a->H; p.W = a->W; p.C = a->C; p.K = a->K; p.kh = a->kh; p.kw = a->kw;
     p.pt = (a->kh - 1) / 2; p.pl = (a->kw - 1) / 2;
     p.ks = a->K; p.koff = 0;
@@ -664,6 +673,7 @@ static int fill_cdna(CdnaP& p, const SavpCdnaArgs* a) {
 static int fill_cdna_multi(CdnaP& p, const SavpCdnaMultiArgs* a) {
     if (!a || a->nsrc < 1 || a->nsrc > MAXS || a->kh * a->kw > MAXTAPS || a->K > MAXK || a->C > MAXC || a->K < 1 || a->C < 1)
         return SAVP_EINVAL;
+    if (!cdna_pad_fits(a->kh, a->kw, a->H, a->W)) return SAVP_EINVAL;
     p.N = a->N; p.H = a->H; p.W = a->W; p.C = a->C; p.K = a->K; p.kh = a->kh; p.kw = a->kw;
     p.pt = (a->kh - 1) / 2; p.pl = (a->kw - 1) / 2;
     p.ks = a->nsrc * a->K; p.koff = 0;

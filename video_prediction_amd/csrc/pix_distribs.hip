@@ -225,6 +225,10 @@ extern "C" int savp_pix_distribs_fwd(void* stream, const SavpPixDistribArgs* a) 
     const int nk = a->nsrc * a->K;
     if (a->tf != SAVP_PIX_TF_FLOW && (a->kh < 1 || a->kw < 1 || a->kh > 64 || a->kw > 64)) return SAVP_EINVAL;
     if (a->tf == SAVP_PIX_TF_CDNA && a->kh * a->kw * nk > PD_MAXK) return SAVP_EINVAL;
+    if (a->tf != SAVP_PIX_TF_FLOW) {                 // tf.pad SYMMETRIC takes a pad of at most the map's size (pd_sym mirrors once)
+        const int pt = (a->kh - 1) / 2, pl = (a->kw - 1) / 2;
+        if (max(pt, a->kh - 1 - pt) > a->H || max(pl, a->kw - 1 - pl) > a->W) return SAVP_EINVAL;
+    }
     if (a->M < nk) return SAVP_EINVAL;
     for (int m = 0; m < a->M; ++m) {
         const int kind = a->slot_kind[m], arg = a->slot_arg[m];

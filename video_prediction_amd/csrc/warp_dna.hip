@@ -261,26 +261,30 @@ __global__ void dna_bwd_kern_kernel(DnaP p) {
     const int y = px / p.W, x = px % p.W;
     const int taps = p.kh * p.kw, pt = (p.kh - 1) / 2, pl = (p.kw - 1) / 2;
     const float* r = p.raw + i * taps * p.ks + p.koff;
-    const float* kn = p.kern + i * taps * p.ks + p.koff;
     float* dr = p.draw + i * taps * p.ks + p.koff;
     const float* im = p.img + (long long)n * p.i_sn;
     const float* d = p.dout + (long long)n * p.do_sn + (long long)px * p.do_sp + p.koff * p.C;
+    // draw = (dkern - sum(dkern * kern)) / s: where one tap holds nearly all of a small s (an even side spreads the identity over 2 or 4
+    // taps of 0.5 / 0.25, within reach of the raw values), that tap's dkern and the dot cancel and 1 / s multiplies what is left.  The
+    // sum, the dot and the difference are therefore taken in float64, with the kernel as v / s rather than its float32-rounded copy.
     for (int k = 0; k < p.K; ++k) {
-        float s = 0.f;
-        for (int t = 0; t < taps; ++t) s += fmaxf(r[t * p.ks + k] + ident5(t / p.kw, t % p.kw, p.kh, p.kw) - RELU_SHIFT, 0.f) + RELU_SHIFT;
-        const float inv = 1.f / s;
-        float dot = 0.f;
+        double s = 0.0;
+        for (int t = 0; t < taps; ++t)
+            s += (double)(fmaxf(r[t * p.ks + k] + ident5(t / p.kw, t % p.kw, p.kh, p.kw) - RELU_SHIFT, 0.f) + RELU_SHIFT);
+        const double inv = 1.0 / s;
+        double dot = 0.0;
         // first pass: dkern (stored temporarily in draw) and its dot with the normalised kernel
         for (int t = 0; t < taps; ++t) {
             const float* q = im + (long long)(symi(y + t / p.kw - pt, p.H) * p.W + symi(x + t % p.kw - pl, p.W)) * p.i_sp;
             float g = 0.f;
             for (int c = 0; c < p.C; ++c) g += q[c] * d[k * p.C + c];
             dr[t * p.ks + k] = g;
-            dot += g * kn[t * p.ks + k];
+            const float v = fmaxf(r[t * p.ks + k] + ident5(t / p.kw, t % p.kw, p.kh, p.kw) - RELU_SHIFT, 0.f) + RELU_SHIFT;
+            dot += (double)g * ((double)v * inv);
         }
         for (int t = 0; t < taps; ++t) {
             const float pre = r[t * p.ks + k] + ident5(t / p.kw, t % p.kw, p.kh, p.kw) - RELU_SHIFT;
-            dr[t * p.ks + k] = pre > 0.f ? (dr[t * p.ks + k] - dot) * inv : 0.f;
+            dr[t * p.ks + k] = pre > 0.f ? (float)(((double)dr[t * p.ks + k] - dot) * inv) : 0.f;
         }
     }
 }
@@ -330,8 +334,16 @@ __global__ void dna_bwd_img_kernel(DnaP p) {
     for (int c = 0; c < p.C; ++c) di[c] = p.dimg_beta ? di[c] + acc[c] : acc[c];
 }
 
+// tf.pad SYMMETRIC takes a pad of at most the image's size (symi() mirrors once): the SAME pads before / after are (k-1)/2 and the rest
+static bool dna_pad_fits(int kh, int kw, int H, int W) {
+    if (kh < 1 || kw < 1) return false;
+    const int pt = (kh - 1) / 2, pl = (kw - 1) / 2;
+    return max(pt, kh - 1 - pt) <= H && max(pl, kw - 1 - pl) <= W;
+}
+
 static int fill_dna(DnaP& p, const SavpDnaArgs* a) {
     if (!a || a->C < 1 || a->C > MAXC || a->K < 1 || !a->img.p || !a->raw || !a->kern) return SAVP_EINVAL;
+    if (!dna_pad_fits(a->kh, a->kw, a->H, a->W)) return SAVP_EINVAL;
     p.N = a->N; p.H = a->H; p.W = a->W; p.C = a->C; p.K = a->K; p.kh = a->kh; p.kw = a->kw;
     p.img = (const float*)a->img.p; p.i_sn = a->img.sn; p.i_sp = a->img.sp;
     p.raw = a->raw; p.kern = a->kern;
@@ -347,6 +359,7 @@ static int fill_dna(DnaP& p, const SavpDnaArgs* a) {
 
 static int fill_dna_multi(DnaP& p, const SavpDnaMultiArgs* a) {
     if (!a || a->C < 1 || a->C > MAXC || a->K < 1 || !a->raw || !a->kern) return SAVP_EINVAL;
+    if (!dna_pad_fits(a->kh, a->kw, a->H, a->W)) return SAVP_EINVAL;
     p.N = a->N; p.H = a->H; p.W = a->W; p.C = a->C; p.K = a->K; p.kh = a->kh; p.kw = a->kw;
     p.ks = a->nsrc * a->K;
     p.raw = a->raw; p.kern = a->kern;

@@ -157,6 +157,18 @@ class ConcatNorm(object):
             self.dbias.zero_()
 
 
+def check_kernel_size(hp):
+    """kernel_size of the CDNA / DNA transformations: sides of at least 1 and at most 49 taps (csrc/cdna_composite.hip keeps 49 per-tap
+    accumulators).  Refused when the model is built -- by the engine before it sizes the kernel heads -- not by the first forward."""
+    if hp.transformation not in ('cdna', 'dna'):
+        return
+    kh, kw = hp.kernel_size
+    if kh < 1 or kw < 1:
+        raise ValueError('kernel_size = %r: both sides must be at least 1' % (tuple(hp.kernel_size),))
+    if kh * kw > 49:
+        raise NotImplementedError('kernel_size = %r: the transformation kernels take at most 49 taps' % (tuple(hp.kernel_size),))
+
+
 class SAVPGenerator(object):
     def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0), pix=0):
         """cond = (n_actions, n_states): widths of inputs['actions'] / inputs['states'] (savp_model.py:411-444): [actions_t | state_t]
@@ -204,6 +216,7 @@ class SAVPGenerator(object):
                                       % (hp.last_frames, lib.MAX_SOURCES))
         if hp.transformation == 'cdna' and hp.num_transformed_images > 8:
             raise NotImplementedError('num_transformed_images = %d: at most 8 CDNA kernels per source frame' % hp.num_transformed_images)
+        check_kernel_size(hp)
         ncol = hp.kernel_size[0] * hp.kernel_size[1] * hp.last_frames * hp.num_transformed_images
         if hp.transformation == 'cdna' and ncol > 256:
             raise NotImplementedError('CDNA head of %d columns (kernel taps x last_frames x num_transformed_images): the dense kernel takes '

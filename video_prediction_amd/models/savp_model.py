@@ -23,7 +23,7 @@ from ..engine import ParamStore, copy_view, add_views
 from .base_model import VideoPredictionModel, learning_rate, kl_weight
 from .hparam_defaults import savp_defaults, SAVP_DEPRECATED_KEYS
 from .networks import PosteriorEncoder, SNDiscriminator
-from .savp_cell import SAVPGenerator
+from .savp_cell import SAVPGenerator, check_kernel_size
 
 
 def _image_shape(images):
@@ -148,6 +148,7 @@ class SAVPEngine(object):
         self.image_shape = tuple(image_shape)
         self.device = torch.device(device)
         self.train = mode == 'train'
+        check_kernel_size(hp)                  # before the kernel heads are sized from it
         specs = V.variable_specs(hp, image_shape, mode=mode, cond=self.cond)
         if values is None:
             values = V.init_variables(specs, seed=seed)
