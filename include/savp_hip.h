@@ -37,7 +37,11 @@ const char* savp_version(void);
  * "inorm_fast_taken" is a counter, not a switch: the number of instance-norm apply passes so far that a shape-specialised kernel ran (the others took
  * the generic kernel); set it to 0 to reset.
  * "splitk_reduced" is a counter, not a switch: the number of convolution calls so far whose requested split-K count was cut (or dropped) because
- * SavpConvArgs.ws was absent or too small (savp_conv_workspace_bytes says how much a call can use); set it to 0 to reset. */
+ * SavpConvArgs.ws was absent or too small (savp_conv_workspace_bytes says how much a call can use); set it to 0 to reset.
+ * "ring_fixed" 1: a ring-kernel call whose planned geometry equals, in every folded value, one of the train step's recurring problems
+ * (csrc/conv_ring_fixed.h) runs that problem's instantiation of the same kernel body with the geometry as compile-time constants; 0: the
+ * generic ring kernel everywhere, same bits.  "ring_fixed_taken" is a counter, not a switch: ring launches so far that took a fixed
+ * instantiation; set it to 0 to reset. */
 int savp_set_option(const char* name, int32_t value);
 int savp_get_option(const char* name, int32_t* value);
 

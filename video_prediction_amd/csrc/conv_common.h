@@ -23,8 +23,9 @@ struct DimGeom {          // one spatial dimension of the (possibly phase-restri
     int srcN;             // source extent (bounds)
 };
 
-__host__ __device__ __forceinline__ DimGeom make_geom(bool dgrad, int f, int In, int Out, int k, int s, int p) {
-    DimGeom g;
+// (constexpr: the fixed-problem table of conv_ring_fixed.h runs the planner's geometry code at compile time)
+__host__ __device__ constexpr __forceinline__ DimGeom make_geom(bool dgrad, int f, int In, int Out, int k, int s, int p) {
+    DimGeom g{};
     if (!dgrad) {
         g.Mdim = Out; g.base = -p; g.mstep = s; g.jstep = 1; g.nt = k; g.t0 = 0; g.tstep = 1;
         g.ob = 0; g.os = 1; g.srcN = In;
@@ -106,14 +107,14 @@ __device__ __forceinline__ int xcd_logical(int b, int n) {
 
 
 // ceil(2^40 / d): magic number of fastdiv()
-static inline unsigned long long magic40(int d) {
+static constexpr inline unsigned long long magic40(int d) {
     if (d <= 0) d = 1;
     return ((1ULL << 40) + (unsigned long long)d - 1ULL) / (unsigned long long)d;
 }
 
 // Launch constants of conv_ring_kernel (ConvP::pre and friends) from the launcher's tiling: identical for every workgroup
 // unless a strided DGRAD splits the output into phases (then pre = 0 and the kernel derives them from blockIdx.y).
-static inline void patch_launch_constants(ConvP& p, const SavpConvArgs* a, int phases, int tih, int nch, int spp, int tW, int splitk) {
+static constexpr inline void patch_launch_constants(ConvP& p, const SavpConvArgs* a, int phases, int tih, int nch, int spp, int tW, int splitk) {
     const bool dg = a->mode == SAVP_CONV_DGRAD;
     int sh_ = 0;
     while ((1 << sh_) < tih) ++sh_;

@@ -26,6 +26,8 @@ enum SavpOptId {
     OPT_INORM_FAST,        // the coalesced instance norm's apply passes take the shape-specialised kernels of inorm_stream_*.hip where one covers the call (1; 0: the generic kernels, same bits; developer: 2 = the forward pass only)
     OPT_INORM_FAST_TAKEN,  // counter, not a switch: apply passes launched on a shape-specialised kernel so far (a test can tell which path a call took)
     OPT_SPLITK_REDUCED,    // counter, not a switch: calls whose requested split-K count was cut (or dropped) because the caller's scratch was too small
+    OPT_RING_FIXED,        // ring kernel: a call whose planned geometry equals a fixed problem's (conv_ring_fixed.h) runs that problem's instantiation, geometry folded at compile time (1; 0: conv_ring_kernel everywhere, same bits)
+    OPT_RING_FIXED_TAKEN,  // counter, not a switch: ring launches that took a fixed instantiation so far
     OPT_COUNT
 };
 

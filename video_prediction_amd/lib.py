@@ -100,10 +100,10 @@ class _LdsPoisonProxy(object):
 
 
 # Kernel-selection switches of the library (include/savp_hip.h: savp_set_option).  The library itself never reads the environment;
-# for A/B runs the host forwards SAVP_<NAME>=<int> here, once, when the library is loaded.  'inorm_fast_taken' and 'splitk_reduced' are counters the library
+# for A/B runs the host forwards SAVP_<NAME>=<int> here, once, when the library is loaded.  'inorm_fast_taken', 'splitk_reduced' and 'ring_fixed_taken' are counters the library
 # increments, not switches: they are in the list to be read (and reset to 0) through get_option / set_option, not to be set from the environment.
 OPTION_NAMES = ('conv_ring', 's2dgrad', 'thin', 'wgp_cfg', 'wgp_split', 'inorm_min_hw', 'colsum_2stage', 'dense_legacy', 'cdna_legacy',
-                'lstm_fused', 'ring_dma', 'lstm_q', 'ring_wwarm', 'wgp_dma', 'ring_early', 'gate_kernel', 'gate_alt', 'gate_cell', 'gate_wwarm', 'inorm_fast', 'inorm_fast_taken', 'splitk_reduced')
+                'lstm_fused', 'ring_dma', 'lstm_q', 'ring_wwarm', 'wgp_dma', 'ring_early', 'gate_kernel', 'gate_alt', 'gate_cell', 'gate_wwarm', 'inorm_fast', 'inorm_fast_taken', 'splitk_reduced', 'ring_fixed', 'ring_fixed_taken')
 
 
 def set_option(name, value):
