@@ -677,7 +677,10 @@ int64_t savp_jpeg_workspace_bytes(const SavpJpegArgs* a);
 /* metrics.py:5-10: mse[t,b] = mean((a-b)^2), psnr[t,b] = -10 log10(mse) (tf.image.psnr, max_val 1); either output may be NULL */
 int savp_frame_mse_psnr(void* stream, const float* a, int64_t a_st, int64_t a_sb, const float* b, int64_t b_st, int64_t b_sb,
                         int32_t T, int32_t B, int32_t inner, float* mse, float* psnr);
-/* metrics.py:13-14: tf.image.ssim(a, b, 1.0) per frame -> out[t,b] (11x11 Gaussian sigma 1.5, k1 .01, k2 .03, VALID) */
+/* metrics.py:13-14: tf.image.ssim(a, b, 1.0) per frame -> out[t,b] (11x11 Gaussian sigma 1.5, k1 .01, k2 .03, VALID).
+ * Frame size: any H >= 11 and 11 <= W <= 744 (SAVP_EINVAL otherwise).  One workgroup per (frame, channel): a plane of up to 8192 pixels is
+ * staged in LDS whole; a larger one in strips of R window rows, R the most whose R + 10 input rows of both planes fit 64 KB (54 at W = 128,
+ * 15 at W = 320, 1 at W = 744).  savp_eval_fold_samples has the same limits and runs the same device code for either size. */
 int savp_frame_ssim(void* stream, const float* a, int64_t a_st, int64_t a_sb, const float* b, int64_t b_st, int64_t b_sb,
                     int32_t T, int32_t B, int32_t H, int32_t W, int32_t C, float* out);
 /* base_model.py:176-190: per batch element, if mean_t(metric) < mean_t(vmin): vmin <- metric (cond_min = 1); likewise max;

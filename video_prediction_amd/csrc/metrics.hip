@@ -5,7 +5,12 @@
 //                        mean over time (sort_criterion :173-174)
 //   select_batch       : base_model.py:170-171,191-196 -- where_axis1 on time-major tensors / running sum of the samples
 // All tensors are time-major [T, B, ...] with explicit (time, batch) strides so that one batch half of the generator's
-// [T, 2B, ...] buffer can be used in place.  HBM-bound, tiny next to the generator unroll; one launch each.
+// [T, 2B, ...] buffer can be used in place.  HBM-bound, tiny next to the generator unroll; one launch each.  SSIM reads every pixel 121
+// times out of LDS and is the largest of them: the fold's SSIM launch is 2.8 % of the kernel time of a parallel evaluation chunk of the
+// 128x128 workload (1.36 ms of 48.2 ms at S = 4, B = 8, 28 future frames; profiles/ssim_large.md).
+// Frame size: SSIM, and with it savp_eval_fold_samples, takes any H >= 11 and 11 <= W <= 744: planes of up to 8192 pixels sit in LDS whole,
+// larger ones are walked in strips of whole rows (ssim_strip_rows); wider rows would need column tiling and are refused.  The other
+// entries take any frame.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "savp_hip.h"
@@ -92,6 +97,59 @@ _Pragma("unroll")                                                               
     }                                                                                                                                      \
     const float RES = block_sum1(acc, sh)
 
+// Planes that do not fit SSIM_LDS_BYTES whole (more than 8192 pixels) are walked in strips of R window rows, ascending: R + SSIM_K - 1 input
+// rows of both planes are staged per strip and every thread carries its sum of lum * cs across the strips into one block_sum1.  The same
+// direct 11x11 window as SSIM_PLANE_SUM; neighbouring strips re-read the SSIM_K - 1 rows they share.
+#define SSIM_LDS_BYTES (64 * 1024)
+// strip geometry shared by the launchers and the kernels: the largest R with [2][R + SSIM_K - 1][W] floats inside SSIM_LDS_BYTES
+// (54 at W = 128, 15 at W = 320); < 1 when not even one window row fits (W > 744)
+__host__ __device__ inline int ssim_strip_rows(int W) { return SSIM_LDS_BYTES / (2 * W * (int)sizeof(float)) - (SSIM_K - 1); }
+static inline size_t ssim_strip_lds(int R, int W) { return (size_t)2 * (R + SSIM_K - 1) * W * sizeof(float); }
+
+//   returns the sum of lum * cs over the Ho x Wo window positions (on every thread); pa / pb as for SSIM_PLANE_SUM, `plane` is
+//   [2][R + SSIM_K - 1][W]
+__device__ __forceinline__ float ssim_strip_sum(const float* pa, const float* pb, int H, int W, int C, float* plane, float* g, float* sh) {
+    const int R = ssim_strip_rows(W);
+    const int Ho = H - SSIM_K + 1, Wo = W - SSIM_K + 1;
+    float* xa = plane;
+    float* xb = plane + (R + SSIM_K - 1) * W;
+    if (threadIdx.x == 0) {                            // the normalised 1-D window of SSIM_PLANE_SUM
+        float s = 0.f, w[SSIM_K];
+        for (int i = 0; i < SSIM_K; ++i) { const float d = (float)i - 0.5f * (SSIM_K - 1); w[i] = expf(-d * d / (2.f * 1.5f * 1.5f)); s += w[i]; }
+        for (int i = 0; i < SSIM_K; ++i) g[i] = w[i] / s;
+    }
+    const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
+    float acc = 0.f;
+    for (int oy0 = 0; oy0 < Ho; oy0 += R) {
+        const int rows_out = min(R, Ho - oy0);         // the last strip may be short
+        const int n_in = (rows_out + SSIM_K - 1) * W;  // input rows oy0 .. oy0 + rows_out + 9 <= H - 1
+        const long long base = (long long)oy0 * W;
+        __syncthreads();                               // the previous strip's windows are done with the planes
+        for (int i = threadIdx.x; i < n_in; i += NT) { xa[i] = pa[(base + i) * C]; xb[i] = pb[(base + i) * C]; }
+        __syncthreads();
+        for (int o = threadIdx.x; o < rows_out * Wo; o += NT) {
+            const int oy = o / Wo, ox = o % Wo;
+            float m0 = 0.f, m1 = 0.f, sxy = 0.f, sqq = 0.f;
+            for (int u = 0; u < SSIM_K; ++u) {
+                float r0 = 0.f, r1 = 0.f, rxy = 0.f, rqq = 0.f;
+                const float* ra = xa + (oy + u) * W + ox;
+                const float* rb = xb + (oy + u) * W + ox;
+#pragma unroll
+                for (int v = 0; v < SSIM_K; ++v) {
+                    const float x = ra[v], y = rb[v], w = g[v];
+                    r0 += w * x; r1 += w * y; rxy += w * x * y; rqq += w * (x * x + y * y);
+                }
+                m0 += g[u] * r0; m1 += g[u] * r1; sxy += g[u] * rxy; sqq += g[u] * rqq;
+            }
+            const float num0 = 2.f * m0 * m1, den0 = m0 * m0 + m1 * m1;
+            const float lum = (num0 + c1) / (den0 + c1);
+            const float cs = (2.f * sxy - num0 + c2) / (sqq - den0 + c2);
+            acc += lum * cs;
+        }
+    }
+    return block_sum1(acc, sh);
+}
+
 // one workgroup per (frame, channel): both planes in LDS, every thread evaluates a strip of window positions
 __global__ __launch_bounds__(NT) void frame_ssim_kernel(const float* a, long long a_st, long long a_sb, const float* b, long long b_st,
                                                         long long b_sb, int B, int H, int W, int C, float* out) {
@@ -104,6 +162,18 @@ __global__ __launch_bounds__(NT) void frame_ssim_kernel(const float* a, long lon
     const float* pb = b + t * b_st + bb * b_sb + c;
     SSIM_PLANE_SUM(s, pa, pb, H, W, C);
     if (threadIdx.x == 0) unsafeAtomicAdd(out + f, s / ((float)(Ho * Wo) * (float)C));
+}
+
+// frame_ssim_kernel for planes of more than 8192 pixels: the same grid and the same add into out, the plane in strips
+__global__ __launch_bounds__(NT) void frame_ssim_strip_kernel(const float* a, long long a_st, long long a_sb, const float* b, long long b_st,
+                                                              long long b_sb, int B, int H, int W, int C, float* out) {
+    extern __shared__ float plane[];                   // [2][R + SSIM_K - 1][W]
+    __shared__ float sh[4];
+    __shared__ float g[SSIM_K];
+    const int f = blockIdx.x / C, c = blockIdx.x % C;
+    const int t = f / B, bb = f % B;
+    const float s = ssim_strip_sum(a + t * a_st + bb * a_sb + c, b + t * b_st + bb * b_sb + c, H, W, C, plane, g, sh);
+    if (threadIdx.x == 0) unsafeAtomicAdd(out + f, s / ((float)((H - SSIM_K + 1) * (W - SSIM_K + 1)) * (float)C));
 }
 
 // single workgroup: per batch element b compare mean_t metric with mean_t vmin / vmax, update min / sum / max
@@ -145,11 +215,17 @@ extern "C" int savp_frame_ssim(void* stream, const float* a, int64_t a_st, int64
                                int32_t T, int32_t B, int32_t H, int32_t W, int32_t C, float* out) {
     if (!a || !b || !out || T < 1 || B < 1 || H < SSIM_K || W < SSIM_K || C < 1) return SAVP_EINVAL;
     const size_t lds = (size_t)2 * H * W * sizeof(float);
-    if (lds > 64 * 1024) return SAVP_EINVAL;
+    const bool strips = lds > SSIM_LDS_BYTES;          // more than 8192 pixels: strips of whole rows
+    const int R = ssim_strip_rows(W);
+    if (strips && (R < 1 || (int64_t)H * W * C > 0x7fffffff)) return SAVP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     savp_zero_async(out, (size_t)T * B * sizeof(float), st);
-    hipLaunchKernelGGL(frame_ssim_kernel, dim3((unsigned)(T * B * C)), dim3(NT), lds, st, a, (long long)a_st, (long long)a_sb, b,
-                       (long long)b_st, (long long)b_sb, B, H, W, C, out);
+    if (strips)
+        hipLaunchKernelGGL(frame_ssim_strip_kernel, dim3((unsigned)(T * B * C)), dim3(NT), ssim_strip_lds(R, W), st, a, (long long)a_st,
+                           (long long)a_sb, b, (long long)b_st, (long long)b_sb, B, H, W, C, out);
+    else
+        hipLaunchKernelGGL(frame_ssim_kernel, dim3((unsigned)(T * B * C)), dim3(NT), lds, st, a, (long long)a_st, (long long)a_sb, b,
+                           (long long)b_st, (long long)b_sb, B, H, W, C, out);
     return LAUNCH_OK();
 }
 
@@ -206,6 +282,20 @@ __global__ __launch_bounds__(NT) void fold_ssim_kernel(const float* tgt, long lo
     const float* pb = pred + f * p_st + n * p_sb + c;
     SSIM_PLANE_SUM(s, pa, pb, H, W, C);
     if (threadIdx.x == 0) part[blockIdx.x] = s / ((float)(Ho * Wo) * (float)C);
+}
+
+// fold_ssim_kernel for planes of more than 8192 pixels: frame_ssim_strip_kernel's device code, the share into its own slot
+__global__ __launch_bounds__(NT) void fold_ssim_strip_kernel(const float* tgt, long long t_st, long long t_sb, const float* pred,
+                                                             long long p_st, long long p_sb, int SB, int B, int H, int W, int C,
+                                                             const int* n_valid, float* part) {
+    extern __shared__ float plane[];                   // [2][R + SSIM_K - 1][W]
+    __shared__ float sh[4];
+    __shared__ float g[SSIM_K];
+    const int fn = blockIdx.x / C, c = blockIdx.x % C;
+    const int f = fn / SB, n = fn % SB;
+    if (n / B >= *n_valid) return;
+    const float s = ssim_strip_sum(tgt + f * t_st + (n % B) * t_sb + c, pred + f * p_st + n * p_sb + c, H, W, C, plane, g, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s / ((float)((H - SSIM_K + 1) * (W - SSIM_K + 1)) * (float)C);
 }
 
 // single workgroup.  Phase 1: ssim[f, n] = sum over c of the channel shares, c ascending from 0 (frame_ssim_kernel adds them to a zeroed
@@ -292,7 +382,9 @@ extern "C" int savp_eval_fold_samples(void* stream, const float* target, int64_t
     const int64_t SB = (int64_t)S * B, inner = (int64_t)H * W * C;
     if (SB * F * C > 0x7fffffff || inner > 0x7fffffff) return SAVP_EINVAL;
     const size_t lds = (size_t)2 * H * W * sizeof(float);
-    if (lds > 64 * 1024) return SAVP_EINVAL;
+    const bool strips = lds > SSIM_LDS_BYTES;          // more than 8192 pixels: strips of whole rows
+    const int R = ssim_strip_rows(W);
+    if (strips && R < 1) return SAVP_EINVAL;
     EvalFoldStates st;
     for (int k = 0; k < SAVP_EVAL_NMETRICS; ++k) {
         const SavpEvalFoldState& m = states[k];
@@ -307,8 +399,12 @@ extern "C" int savp_eval_fold_samples(void* stream, const float* target, int64_t
     hipLaunchKernelGGL(fold_mse_kernel, dim3((unsigned)(F * SB)), dim3(NT), 0, sm, target, (long long)t_st, (long long)t_sb, fut,
                        (long long)p_st, (long long)p_sb, (int)SB, B, (int)inner, n_valid, met + SAVP_EVAL_PSNR * F * SB,
                        met + SAVP_EVAL_MSE * F * SB);
-    hipLaunchKernelGGL(fold_ssim_kernel, dim3((unsigned)(F * SB * C)), dim3(NT), lds, sm, target, (long long)t_st, (long long)t_sb, fut,
-                       (long long)p_st, (long long)p_sb, (int)SB, B, H, W, C, n_valid, part);
+    if (strips)
+        hipLaunchKernelGGL(fold_ssim_strip_kernel, dim3((unsigned)(F * SB * C)), dim3(NT), ssim_strip_lds(R, W), sm, target, (long long)t_st,
+                           (long long)t_sb, fut, (long long)p_st, (long long)p_sb, (int)SB, B, H, W, C, n_valid, part);
+    else
+        hipLaunchKernelGGL(fold_ssim_kernel, dim3((unsigned)(F * SB * C)), dim3(NT), lds, sm, target, (long long)t_st, (long long)t_sb, fut,
+                           (long long)p_st, (long long)p_sb, (int)SB, B, H, W, C, n_valid, part);
     hipLaunchKernelGGL(fold_select_kernel, dim3(1), dim3(NT), 0, sm, met, (const float*)part, F, (int)SB, B, C, n_valid, st, sel);
     unsigned gx = (unsigned)((inner + NT * 4 - 1) / (NT * 4));
     if (gx > 64) gx = 64;

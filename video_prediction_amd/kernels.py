@@ -1680,12 +1680,28 @@ def frame_mse_psnr(a, b, mse=None, psnr=None):
                                        _p(psnr)), 'savp_frame_mse_psnr')
 
 
+SSIM_WINDOW = 11                                  # metrics.hip SSIM_K
+SSIM_MAX_W = 64 * 1024 // (2 * 4 * SSIM_WINDOW)   # 744: the widest row of which 11 fit metrics.hip's 64 KB of LDS for both planes
+
+
+def _check_ssim_geometry(name, H, W):
+    """savp_frame_ssim / savp_eval_fold_samples refuse these with a bare SAVP_EINVAL; say which limit it was."""
+    if H < SSIM_WINDOW:
+        raise ValueError('%s: H=%d, W=%d: SSIM needs H >= %d (its window is %dx%d)' % (name, H, W, SSIM_WINDOW, SSIM_WINDOW, SSIM_WINDOW))
+    if W < SSIM_WINDOW:
+        raise ValueError('%s: H=%d, W=%d: SSIM needs W >= %d (its window is %dx%d)' % (name, H, W, SSIM_WINDOW, SSIM_WINDOW, SSIM_WINDOW))
+    if W > SSIM_MAX_W:
+        raise ValueError('%s: H=%d, W=%d: SSIM needs W <= %d (%d rows of both planes must fit 64 KB of LDS)'
+                         % (name, H, W, SSIM_MAX_W, SSIM_WINDOW))
+
+
 def frame_ssim(a, b, out):
-    """metrics.py:13-14 (tf.image.ssim, max_val 1) per frame of [T, B, H, W, C] tensors -> out [T, B]."""
+    """metrics.py:13-14 (tf.image.ssim, max_val 1) per frame of [T, B, H, W, C] tensors -> out [T, B].  Any H >= 11, 11 <= W <= 744."""
     lib.require_device(a, b, out)
     a_st, a_sb, _ = _tb(a)
     b_st, b_sb, _ = _tb(b)
     T, B, H, W, C = a.shape
+    _check_ssim_geometry('frame_ssim', H, W)
     lib.check(_L().savp_frame_ssim(lib.stream(), _p(a), a_st, a_sb, _p(b), b_st, b_sb, T, B, H, W, C, _p(out)), 'savp_frame_ssim')
 
 
@@ -1730,6 +1746,7 @@ def eval_fold_samples(target, pred, n_valid, states, ws):
     T1, SB = pred.shape[:2]
     if tuple(pred.shape[2:]) != (H, W, C) or SB % B or T1 < F:
         raise ValueError('eval_fold_samples: pred %r does not fit target %r' % (tuple(pred.shape), tuple(target.shape)))
+    _check_ssim_geometry('eval_fold_samples', H, W)
     S = SB // B
     t_st, t_sb, _ = _tb(target)
     p_st, p_sb, _ = _tb(pred)
