@@ -635,6 +635,21 @@ int savp_convgru_gates_fwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_out_fwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_out_bwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_gates_bwd(void* stream, const SavpGruArgs* a);
+/* The same four blocks of the cell WITHOUT a normaliser (normalizer_fn = None, rnn_ops.py:214-224: conv_rnn_norm_layer = 'none' and
+ * ablation_conv_rnn_norm).  `pre` is the convolution's output INCLUDING its bias; gamma, beta, mean, rstd, eps, dgamma and dbeta are
+ * not read.
+ *  gates fwd : r = sigmoid(pre[..., :F]), u = sigmoid(pre[..., F:]); writes u and r*h
+ *  out fwd   : c = tanh(pre); h' = u*h + (1-u)*c written to nout destinations
+ *  out bwd   : dh' = sum of the ndy views; dpre = dh'*(1-u)*(1-c^2); du = dh'*(h-c); dh = dh'*u (overwrites)
+ *  gates bwd : dpre[..., F:] = du*u*(1-u); dpre[..., :F] = drh*h*r*(1-r); dh += drh*r (accumulates)
+ * Pointwise: one thread per 4 channels of a pixel, float4 accesses, a grid-stride loop -- any plane size (no HW <= 1024 limit), no
+ * workspace, no atomics (bit-reproducible, safe in a captured graph).  SAVP_EINVAL: F % 4 != 0, N or HW < 1, a null pointer among those
+ * the entry reads or writes, or a base pointer / view stride that breaks 16-byte access (pointers 16-byte aligned, sn and sp multiples
+ * of 4 floats). */
+int savp_convgru_plain_gates_fwd(void* stream, const SavpGruArgs* a);
+int savp_convgru_plain_out_fwd(void* stream, const SavpGruArgs* a);
+int savp_convgru_plain_out_bwd(void* stream, const SavpGruArgs* a);
+int savp_convgru_plain_gates_bwd(void* stream, const SavpGruArgs* a);
 
 /* uint8 frames [B, T, frame] -> float32 time-major [T, B, frame] * (1/255): tf.image.convert_image_dtype (base_dataset.py:187)
  * + transpose_batch_time (tf_utils.py:118-122) for batches delivered by libsavp_io.so (include/savp_io.h); frame % 4 == 0 */

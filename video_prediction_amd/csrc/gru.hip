@@ -6,6 +6,7 @@
 //                                                                         input slot (the reference's quirk: the candidate
 //                                                                         conv sees [x, h, r*h], rnn_ops.py:242,258)
 //   output stage: c = tanh(IN_F(conv5x5([x, h, r*h]))) ; h' = u*h + (1-u)*c
+// The same blocks of the cell without a normaliser are pointwise and stand at the end of the file (savp_convgru_plain_*).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "savp_hip.h"
@@ -307,8 +308,8 @@ __global__ __launch_bounds__(NT) void gru_gates_bwd_kernel(GruP p) {
     }
 }
 
-static int fill_gru(GruP& p, const SavpGruArgs* a) {
-    if (!a || a->F % 4 || a->HW < 1 || a->HW > MAXPPT * NT || !a->pre || !a->h.p) return SAVP_EINVAL;
+static int fill_gru(GruP& p, const SavpGruArgs* a, bool any_plane = false) {
+    if (!a || a->F % 4 || a->HW < 1 || (!any_plane && a->HW > MAXPPT * NT) || !a->pre || !a->h.p) return SAVP_EINVAL;
     if (a->nout < 0 || a->nout > 4 || a->ndy < 0 || a->ndy > 4) return SAVP_EINVAL;
     p.N = a->N; p.HW = a->HW; p.F = a->F; p.eps = a->eps;
     p.pre = a->pre;
@@ -340,3 +341,137 @@ GRU_ENTRY(savp_convgru_gates_fwd, gru_gates_fwd_kernel, p.u && p.rh && p.mean &&
 GRU_ENTRY(savp_convgru_out_fwd, gru_out_fwd_kernel, p.u && p.nout >= 1 && p.mean && p.rstd)
 GRU_ENTRY(savp_convgru_out_bwd, gru_out_bwd_kernel, p.u && p.du && p.dpre && p.dh && p.ndy >= 1 && p.dgamma && p.dbeta)
 GRU_ENTRY(savp_convgru_gates_bwd, gru_gates_bwd_kernel, p.du && p.dpre && p.dh && p.drh && p.dgamma && p.dbeta)
+
+// ------------------------------------------------------------------------------------------------------------
+// The cell without a normaliser (normalizer_fn = None, rnn_ops.py:220-223: the two convolutions then carry a bias, which `pre` already
+// holds): pointwise, like lstm_plain_*_kernel in norm_lstm.hip.  A thread owns 4 channels of one pixel; float4 accesses; a grid-stride
+// loop over N * HW * F/4 items, so any plane size, no workspace, no atomics.  SavpGruArgs' gamma / beta / mean / rstd / eps / dgamma /
+// dbeta are not read.
+//   gates fwd : r = sigmoid(pre[..., :F]), u = sigmoid(pre[..., F:]) -> u saved, r*h into the candidate conv's input slot
+//   out fwd   : c = tanh(pre); h' = u*h + (1-u)*c to nout destinations
+//   out bwd   : dh' = sum dy_k; dpre = dh'*(1-u)*(1-c^2); du = dh'*(h-c); dh = dh'*u (overwrites)
+//   gates bwd : dpre[..., F:] = du*u*(1-u); dpre[..., :F] = drh*h*r*(1-r); dh += drh*r
+// ------------------------------------------------------------------------------------------------------------
+#define PLAIN_MAX_BLOCKS 2048            // 256 CUs x 8 workgroups of a streaming kernel; the loop strides over the rest
+
+#define PLAIN_ITEM()                                                                                                  \
+    const int c0 = (int)(i % F4) * 4;                                                                                 \
+    const long long px = i / F4;                       /* n * HW + pixel */                                           \
+    const int n = (int)(px / p.HW), q = (int)(px - (long long)n * p.HW)
+
+__global__ __launch_bounds__(NT) void gru_plain_gates_fwd_kernel(GruP p) {
+    const int F4 = p.F >> 2;
+    const long long total = (long long)p.N * p.HW * F4;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+        PLAIN_ITEM();
+        const float* g = p.pre + px * 2 * p.F + c0;
+        const float4 gr = ld4(g), gu = ld4(g + p.F);
+        const float4 h4 = ld4(p.h + (long long)n * p.h_sn + (long long)q * p.h_sp + c0);
+        const float4 u4 = make_float4(sigm(gu.x), sigm(gu.y), sigm(gu.z), sigm(gu.w));
+        st4(p.rh + (long long)n * p.rh_sn + (long long)q * p.rh_sp + c0,
+            make_float4(sigm(gr.x) * h4.x, sigm(gr.y) * h4.y, sigm(gr.z) * h4.z, sigm(gr.w) * h4.w));
+        st4(p.u + px * p.F + c0, u4);
+    }
+}
+
+__global__ __launch_bounds__(NT) void gru_plain_out_fwd_kernel(GruP p) {
+    const int F4 = p.F >> 2;
+    const long long total = (long long)p.N * p.HW * F4;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+        PLAIN_ITEM();
+        const float4 g4 = ld4(p.pre + px * p.F + c0);
+        const float4 h4 = ld4(p.h + (long long)n * p.h_sn + (long long)q * p.h_sp + c0);
+        const float4 u4 = ld4(p.u + px * p.F + c0);
+        const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, hv[4] = {h4.x, h4.y, h4.z, h4.w}, uv[4] = {u4.x, u4.y, u4.z, u4.w};
+        float o[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[c] = uv[c] * hv[c] + (1.f - uv[c]) * tanh_(gv[c]);
+        const float4 o4 = make_float4(o[0], o[1], o[2], o[3]);
+        for (int k = 0; k < p.nout; ++k) st4(p.out[k] + (long long)n * p.o_sn[k] + (long long)q * p.o_sp[k] + c0, o4);
+    }
+}
+
+__global__ __launch_bounds__(NT) void gru_plain_out_bwd_kernel(GruP p) {
+    const int F4 = p.F >> 2;
+    const long long total = (long long)p.N * p.HW * F4;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+        PLAIN_ITEM();
+        const float4 g4 = ld4(p.pre + px * p.F + c0);
+        const float4 h4 = ld4(p.h + (long long)n * p.h_sn + (long long)q * p.h_sp + c0);
+        const float4 u4 = ld4(p.u + px * p.F + c0);
+        float4 d4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int k = 0; k < p.ndy; ++k) {
+            const float4 t = ld4(p.dy[k] + (long long)n * p.dy_sn[k] + (long long)q * p.dy_sp[k] + c0);
+            d4.x += t.x; d4.y += t.y; d4.z += t.z; d4.w += t.w;
+        }
+        const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, hv[4] = {h4.x, h4.y, h4.z, h4.w}, uv[4] = {u4.x, u4.y, u4.z, u4.w},
+                    dv[4] = {d4.x, d4.y, d4.z, d4.w};
+        float dz[4], duv[4], dhv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float cnd = tanh_(gv[c]);
+            dz[c] = dv[c] * (1.f - uv[c]) * (1.f - cnd * cnd);
+            duv[c] = dv[c] * (hv[c] - cnd);
+            dhv[c] = dv[c] * uv[c];
+        }
+        st4(p.dpre + px * p.F + c0, make_float4(dz[0], dz[1], dz[2], dz[3]));
+        st4(p.du + px * p.F + c0, make_float4(duv[0], duv[1], duv[2], duv[3]));
+        // OVERWRITES its dh destination (u * dh'); gates_bwd accumulates into its own
+        st4(p.dh + (long long)n * p.dh_sn + (long long)q * p.dh_sp + c0, make_float4(dhv[0], dhv[1], dhv[2], dhv[3]));
+    }
+}
+
+__global__ __launch_bounds__(NT) void gru_plain_gates_bwd_kernel(GruP p) {
+    const int F4 = p.F >> 2;
+    const long long total = (long long)p.N * p.HW * F4;
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+        PLAIN_ITEM();
+        const float* g = p.pre + px * 2 * p.F + c0;
+        const float4 gr = ld4(g), gu = ld4(g + p.F);
+        const float4 h4 = ld4(p.h + (long long)n * p.h_sn + (long long)q * p.h_sp + c0);
+        const float4 d4 = ld4(p.drh + (long long)n * p.drh_sn + (long long)q * p.drh_sp + c0);
+        const float4 du4 = ld4(p.du + px * p.F + c0);
+        float* dh = p.dh + (long long)n * p.dh_sn + (long long)q * p.dh_sp + c0;
+        const float4 a4 = ld4(dh);
+        const float rv[4] = {gr.x, gr.y, gr.z, gr.w}, uv[4] = {gu.x, gu.y, gu.z, gu.w}, hv[4] = {h4.x, h4.y, h4.z, h4.w},
+                    drhv[4] = {d4.x, d4.y, d4.z, d4.w}, duv[4] = {du4.x, du4.y, du4.z, du4.w}, av[4] = {a4.x, a4.y, a4.z, a4.w};
+        float dr[4], dU[4], dhv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float rr = sigm(rv[c]), uu = sigm(uv[c]);
+            dr[c] = drhv[c] * hv[c] * rr * (1.f - rr);
+            dU[c] = duv[c] * uu * (1.f - uu);
+            dhv[c] = av[c] + drhv[c] * rr;
+        }
+        st4(dh, make_float4(dhv[0], dhv[1], dhv[2], dhv[3]));
+        float* d = p.dpre + px * 2 * p.F + c0;
+        st4(d, make_float4(dr[0], dr[1], dr[2], dr[3]));
+        st4(d + p.F, make_float4(dU[0], dU[1], dU[2], dU[3]));
+    }
+}
+
+// a float4 at every (sample, pixel, 4-channel group) of a view needs a 16-byte base and strides that are multiples of 4 floats
+static bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
+static bool view_ok(const void* q, long long sn, long long sp) { return q && al16(q) && sn % 4 == 0 && sp % 4 == 0; }
+
+#define GRU_PLAIN_ENTRY(name, kernel, cond)                                                                        \
+    extern "C" int name(void* stream, const SavpGruArgs* a) {                                                      \
+        GruP p;                                                                                                     \
+        int rc = fill_gru(p, a, true);                                                                              \
+        if (rc) return rc;                                                                                          \
+        if (a->N < 1 || !al16(p.pre) || !view_ok(p.h, p.h_sn, p.h_sp) || !(cond)) return SAVP_EINVAL;              \
+        for (int k = 0; k < p.nout; ++k) if (!view_ok(p.out[k], p.o_sn[k], p.o_sp[k])) return SAVP_EINVAL;         \
+        for (int k = 0; k < p.ndy; ++k) if (!view_ok(p.dy[k], p.dy_sn[k], p.dy_sp[k])) return SAVP_EINVAL;         \
+        const long long total = (long long)a->N * a->HW * (a->F / 4);                                              \
+        long long blocks = (total + NT - 1) / NT;                                                                   \
+        if (blocks > PLAIN_MAX_BLOCKS) blocks = PLAIN_MAX_BLOCKS;                                                   \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, p);                    \
+        return LAUNCH_OK();                                                                                         \
+    }
+GRU_PLAIN_ENTRY(savp_convgru_plain_gates_fwd, gru_plain_gates_fwd_kernel,
+                p.u && al16(p.u) && view_ok(p.rh, p.rh_sn, p.rh_sp))
+GRU_PLAIN_ENTRY(savp_convgru_plain_out_fwd, gru_plain_out_fwd_kernel, p.u && al16(p.u) && p.nout >= 1)
+GRU_PLAIN_ENTRY(savp_convgru_plain_out_bwd, gru_plain_out_bwd_kernel,
+                p.u && al16(p.u) && p.du && al16(p.du) && p.dpre && al16(p.dpre) && view_ok(p.dh, p.dh_sn, p.dh_sp) && p.ndy >= 1)
+GRU_PLAIN_ENTRY(savp_convgru_plain_gates_bwd, gru_plain_gates_bwd_kernel,
+                p.du && al16(p.du) && p.dpre && al16(p.dpre) && view_ok(p.dh, p.dh_sn, p.dh_sp) && view_ok(p.drh, p.drh_sn, p.drh_sp))

@@ -1644,6 +1644,36 @@ def convgru_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma
     acc.finish()
 
 
+# the cell without a normaliser: `pre` holds the convolution's output with its bias; pointwise, any plane size
+def convgru_plain_gates_fwd(pre, h, u, rh):
+    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1] // 2, 0.0)
+    a.u, a.rh = _p(u), view(rh)
+    lib.check(_L().savp_convgru_plain_gates_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_gates_fwd')
+
+
+def convgru_plain_out_fwd(pre, h, u, outs):
+    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1], 0.0)
+    a.u = _p(u)
+    a.nout = len(outs)
+    _set_views(a.out, outs)
+    lib.check(_L().savp_convgru_plain_out_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_out_fwd')
+
+
+def convgru_plain_out_bwd(pre, h, u, dys, dpre, du, dh):
+    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1], 0.0)
+    a.u = _p(u)
+    a.ndy = len(dys)
+    _set_views(a.dy, dys)
+    a.dpre, a.du, a.dh = _p(dpre), _p(du), view(dh)
+    lib.check(_L().savp_convgru_plain_out_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_out_bwd')
+
+
+def convgru_plain_gates_bwd(pre, h, du, drh, dpre, dh):
+    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1] // 2, 0.0)
+    a.du, a.drh, a.dpre, a.dh = _p(du), view(drh), _p(dpre), view(dh)
+    lib.check(_L().savp_convgru_plain_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_gates_bwd')
+
+
 GAN_TYPES = {'LSGAN': 0, 'GAN': 1, 'SNGAN': 2}
 
 

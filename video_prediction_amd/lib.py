@@ -468,7 +468,8 @@ class SavpGruArgs(ctypes.Structure):
                 ('dh', SavpView), ('drh', SavpView), ('dgamma', c_vp), ('dbeta', c_vp)]
 
 
-for _n in ('savp_convgru_gates_fwd', 'savp_convgru_out_fwd', 'savp_convgru_out_bwd', 'savp_convgru_gates_bwd'):
+for _n in ('savp_convgru_gates_fwd', 'savp_convgru_out_fwd', 'savp_convgru_out_bwd', 'savp_convgru_gates_bwd',
+           'savp_convgru_plain_gates_fwd', 'savp_convgru_plain_out_fwd', 'savp_convgru_plain_out_bwd', 'savp_convgru_plain_gates_bwd'):
     register(_n, [c_vp, ctypes.POINTER(SavpGruArgs)])
 register('savp_gan_loss', [c_vp, c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_i32])
 register('savp_fold_f64', [c_vp, c_vp, c_i64, c_vp, c_vp])

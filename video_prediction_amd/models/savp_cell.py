@@ -43,7 +43,8 @@ def check_norm_layers(hp):
         raise NotImplementedError("use_tile_concat=False with norm_layer=%r, conv_rnn_norm_layer=%r: the untiled latent is only "
                                   "cancelled by an instance norm" % (hp.norm_layer, hp.conv_rnn_norm_layer))
     if hp.conv_rnn_norm_layer == 'layer' and not hp.ablation_rnn:
-        if hp.conv_rnn == 'gru':
+        # (under ablation_conv_rnn_norm the cell itself has no normaliser and the layer norm sits on the layer's output: covered)
+        if hp.conv_rnn == 'gru' and not hp.ablation_conv_rnn_norm:
             raise NotImplementedError("conv_rnn='gru' with conv_rnn_norm_layer='layer': the GRU gate kernels are instance-norm only")
 
 
@@ -190,15 +191,14 @@ class SAVPGenerator(object):
         # conv_rnn_norm_layer = 'layer' inside the ConvLSTM cell (separate_norms, rnn_ops.py:147-165): the gate convolution (no bias),
         # a layer norm per gate (one G = 4 launch), the pointwise state update, a layer norm of the new state, h' (csrc/ln_lstm.hip)
         self.cell_ln = bool(hp.conv_rnn_norm_layer == 'layer' and not hp.ablation_conv_rnn_norm)
-        # The ConvLSTM cell WITHOUT a normaliser (rnn_ops.py:122-125: the gate convolution then has a bias; :148-165 with normalizer_fn None):
+        # The conv-RNN cell WITHOUT a normaliser (ConvLSTM, rnn_ops.py:122-125: the gate convolution then has a bias; :148-165 with
+        # normalizer_fn None.  ConvGRU, :220-223: both convolutions have one, gates/bias and candidate/bias; :246-263 with normalizer_fn None):
         # conv_rnn_norm_layer = 'none', or ablation_conv_rnn_norm (savp_model.py:380-384: the cell is built without one and the layer's OUTPUT
         # h -- not the state handed to the next step -- goes through normalizer_fn, variables under <cell scope>/InstanceNorm/).
         self.cell_plain = bool(hp.conv_rnn_norm_layer == 'none' or hp.ablation_conv_rnn_norm)
         self.out_norm = bool(hp.ablation_conv_rnn_norm)
         if self.out_norm and hp.conv_rnn_norm_layer == 'none':
             raise TypeError("ablation_conv_rnn_norm with conv_rnn_norm_layer='none': the reference calls normalizer_fn = None (savp_model.py:384)")
-        if self.cell_plain and hp.conv_rnn != 'lstm' and not hp.ablation_rnn:
-            raise NotImplementedError('the normaliser-free cell is on the HIP path for conv_rnn = lstm only')
         # downsample_layer / upsample_layer / activation_layer (ops.py:1052-1098; savp_model.py:395-397).  conv2d: the strided SAME
         # convolution, ConvLayer kind 'down'; deconv2d: conv2d_transpose, kind 'deconv'; the _v2 names are aliases (variables.DOWN_SCOPES).
         # elu: the activation code of every norm_layer site of the cell (the ladder, ablation_rnn's conv_h<i>, the 3x3 heads).
@@ -252,6 +252,11 @@ class SAVPGenerator(object):
         # z, the `dense/kernel` / `weights` variables and z itself get zero gradients.  The layers therefore run without z channels and
         # those variables keep their (zero-initialised) gradients; pinned against the oracle, which computes the sums literally.
         tile = bool(hp.use_tile_concat)
+        if hp.conv_rnn == 'gru' and self.cell_plain and not self.abl_rnn and not tile and hp.where_add == 'all' and zw:
+            # no norm stands behind the bare cell's two convolutions, so dense(z) (gates/weights, candidate/weights) is NOT cancelled there
+            raise NotImplementedError("conv_rnn='gru' without a cell normaliser (conv_rnn_norm_layer='none' or ablation_conv_rnn_norm) with "
+                                      "use_tile_concat=False, where_add='all' and a latent: the untiled latent of the bare cell is not on "
+                                      "the HIP path")
         zr = zw if (hp.where_add == 'all' and tile) else 0              # tiled channels in a conv-RNN's input [x | actions state z | h]
         g = train
         # bf16 storage of tensors whose ONLY readers are convolutions of the bf16 datapath (round 4; the cell input [x | z | h] and the
@@ -326,10 +331,16 @@ class SAVPGenerator(object):
                 L['u'] = torch.empty(T1, N, h_, w_, f, device=dev)
                 L['du'] = torch.empty(N, h_, w_, f, device=dev) if g else None
                 L['dh_tmp'] = torch.empty(N, h_, w_, f, device=dev) if g else None
-                L['rconv'] = ConvLayer(store, r + 'gates/kernel', None, 'conv', (5, 5), (1, 1), (2, 2))
-                L['cconv'] = ConvLayer(store, r + 'candidate/kernel', None, 'conv', (5, 5), (1, 1), (2, 2))
-                L['n1'] = Norm(store, r + 'gates/reset_update/', T1, N, 2 * f, dev)
-                L['n2'] = Norm(store, r + 'candidate/state/', T1, N, f, dev)
+                # without a normaliser the two convolutions carry a bias (rnn_ops.py:220-223) and the gate blocks are pointwise
+                L['rconv'] = ConvLayer(store, r + 'gates/kernel', (r + 'gates/bias') if self.cell_plain else None, 'conv', (5, 5), (1, 1), (2, 2))
+                L['cconv'] = ConvLayer(store, r + 'candidate/kernel', (r + 'candidate/bias') if self.cell_plain else None, 'conv', (5, 5),
+                                       (1, 1), (2, 2))
+                if not self.cell_plain:
+                    L['n1'] = Norm(store, r + 'gates/reset_update/', T1, N, 2 * f, dev)
+                    L['n2'] = Norm(store, r + 'candidate/state/', T1, N, f, dev)
+                if self.out_norm:          # ablation_conv_rnn_norm: normalizer_fn(h) on the layer's output, the state stays un-normalised
+                    L['h_raw'] = Act((T1, N, h_, w_, f), dev, grad=g)
+                    L['onorm'] = self._norm(prefix + 'gru_h%d/' % i, f, hp.conv_rnn_norm_layer)
             elif use_rnn:
                 r = prefix + 'lstm_h%d/basic_conv2dlstm_cell/' % i
                 # fused ConvLSTM cell of the bf16 datapath: the gate convolution's epilogue produces the statistics of the first
@@ -721,16 +732,25 @@ class SAVPGenerator(object):
                     hs, rs_, cin1 = f + L['zr'], f + L['zr'] + f, L['cin1']
                     norm_fwd(nrm, L['pre'].v[t], [a.v[t][..., 0:f]], nrm.mean[t], nrm.rstd[t],
                              act=self.act, eps=EPS_IN, stats=st, stats_shift=L['conv'].bias if st is not None else None)
-                    n1, n2 = L['n1'], L['n2']
                     hprev = a.v[t][..., hs:hs + f]
+                    nxt_h = [a.v[t + 1][..., hs:hs + f]] if t + 1 < T1 else []
+                    if self.cell_plain:
+                        L['rconv'].forward(a.v[t][..., 0:cin1], L['gates'].v[t])              # conv + bias
+                        K.convgru_plain_gates_fwd(L['gates'].v[t], hprev, L['u'][t], a.v[t][..., rs_:rs_ + f])
+                        L['cconv'].forward(a.v[t], L['cand'].v[t])                            # conv + bias
+                        hdst = ([L['h_raw'].v[t]] if self.out_norm else self._out_views(L, t)) + nxt_h
+                        K.convgru_plain_out_fwd(L['cand'].v[t], hprev, L['u'][t], hdst)
+                        if self.out_norm:
+                            on = L['onorm']
+                            norm_fwd(on, L['h_raw'].v[t], self._out_views(L, t), on.mean[t], on.rstd[t], act='none', eps=EPS_IN)
+                        continue
+                    n1, n2 = L['n1'], L['n2']
                     L['rconv'].forward(a.v[t][..., 0:cin1], L['gates'].v[t], use_bias=False)
                     K.convgru_gates_fwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['u'][t],
                                         a.v[t][..., rs_:rs_ + f], eps=EPS_IN)
                     L['cconv'].forward(a.v[t], L['cand'].v[t], use_bias=False)
-                    outs = self._out_views(L, t)
-                    if t + 1 < T1:
-                        outs.append(a.v[t + 1][..., hs:hs + f])
-                    K.convgru_out_fwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], outs, eps=EPS_IN)
+                    K.convgru_out_fwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t],
+                                      self._out_views(L, t) + nxt_h, eps=EPS_IN)
                 elif L['rnn'] and self.cell_plain:
                     a = L['a']
                     self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, [a.v[t][..., 0:f]], t)
@@ -1026,17 +1046,29 @@ class SAVPGenerator(object):
                 if L['rnn'] and self.gru:
                     a = L['a']
                     hs, rs_, cin1 = f + L['zr'], f + L['zr'] + f, L['cin1']
+                    if self.out_norm:
+                        on = L['onorm']
+                        norm_bwd(on, L['h_raw'].v[t], self._out_views(L, t)[0], on.mean[t], on.rstd[t], dys,
+                                 L['h_raw'].g[t], on.dgamma, on.dbeta, act='none', eps=EPS_IN)
+                        dys = [L['h_raw'].g[t]]
                     if t + 1 < T1:
                         dys.append(a.g[t + 1][..., hs:hs + f])
-                    n1, n2 = L['n1'], L['n2']
                     hprev = a.v[t][..., hs:hs + f]
-                    K.convgru_out_bwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], dys,
-                                      L['cand'].g[t], L['du'], L['dh_tmp'], n2.dgamma, n2.dbeta, eps=EPS_IN)
+                    if self.cell_plain:
+                        K.convgru_plain_out_bwd(L['cand'].v[t], hprev, L['u'][t], dys, L['cand'].g[t], L['du'], L['dh_tmp'])
+                    else:
+                        n1, n2 = L['n1'], L['n2']
+                        K.convgru_out_bwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], dys,
+                                          L['cand'].g[t], L['du'], L['dh_tmp'], n2.dgamma, n2.dbeta, eps=EPS_IN)
                     L['cconv'].backward_data(L['cand'].g[t], a.g[t], beta=0)
                     add_views([L['dh_tmp']], a.g[t][..., hs:hs + f])
-                    K.convgru_gates_bwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'],
-                                        a.g[t][..., rs_:rs_ + f], L['gates'].g[t], a.g[t][..., hs:hs + f], n1.dgamma, n1.dbeta,
-                                        eps=EPS_IN)
+                    if self.cell_plain:
+                        K.convgru_plain_gates_bwd(L['gates'].v[t], hprev, L['du'], a.g[t][..., rs_:rs_ + f], L['gates'].g[t],
+                                                  a.g[t][..., hs:hs + f])
+                    else:
+                        K.convgru_gates_bwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'],
+                                            a.g[t][..., rs_:rs_ + f], L['gates'].g[t], a.g[t][..., hs:hs + f], n1.dgamma, n1.dbeta,
+                                            eps=EPS_IN)
                     L['rconv'].backward_data(L['gates'].g[t], a.g[t][..., 0:cin1], beta=1)
                     norm_bwd(nrm, L['pre'].v[t], a.v[t][..., 0:f], nrm.mean[t], nrm.rstd[t],
                                        [a.g[t][..., 0:f]], L['pre'].g[t], nrm.dgamma, nrm.dbeta, act=self.act, eps=EPS_IN)
