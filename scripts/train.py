@@ -14,16 +14,24 @@ What TensorFlow did implicitly is explicit here: one `model.train_step(inputs)` 
 Summaries (:247-321) go to two places.  <output_dir>/summaries.jsonl gets JSON lines: the training scalars every --summary_freq steps and
 one best-of-N row per --eval_summary_freq on a validation batch.  <output_dir>/events.out.tfevents.<time>.<host> is a TensorBoard event
 file (video_prediction_amd/summaries.py), opened at the first write: at --summary_freq the scalars of the training batch (losses, psnr /
-mse / ssim / lpips of a prior unroll, ground_truth_sampling_mean) and of a validation batch (tag suffix _1; metrics only: the losses
-exist only inside a train step here); at --image_summary_freq the GIF boards of images, gen_images, transformed_images, masks and
+mse / ssim / lpips of a prior unroll, ground_truth_sampling_mean) and of a validation batch (tag suffix _1; its losses -- g_loss_1,
+d_loss_1, gen_l1_loss_1, gen_kl_loss_1, ... -- come from a forward-only pass at the current weights, SAVPEngine.eval_losses: the
+reference's summary_op run with the validation handle, train.py:270-289); at --image_summary_freq the GIF boards of images, gen_images, transformed_images, masks and
 gen_flows_rgb (+ _enc) for both batches, built on the GPU (csrc/summary.hip) and copied out as uint8 through a pinned buffer; at
 --eval_summary_freq the best / mean / worst GIF boards and metric scalars of eval_num_samples prior samples for both batches; at the
 multiples of --accum_eval_summary_freq the eval metrics averaged over num_examples_per_epoch() // batch_size validation batches
-(accum_..._1; unlike the reference not also at the last iteration, see should_accum_eval).  Not written: the pr_curve-hack plots,
-boards of gen_images_samples, the long_sequence_length model's accumulated evaluation, histograms, graph defs.  A summary pass changes
-no variable, Adam moment or noise stream, so a run's checkpoints do not depend on the frequencies.
+(accum_..._1; unlike the reference not also at the last iteration, see should_accum_eval) and, when the validation dataset's
+long_sequence_length differs from its sequence_length (BAIR 12 / 30, KTH 20 / 40; see long_eval_length), the same for a second,
+test-mode model of that length that reads the training model's variables (build_graph(share_with=model); tags accum_..._2,
+train.py:136-145,176-191,301-318).  The long model and its dataset iterator both run at a per-GPU batch of max(1, per_gpu // 2), so one
+accumulated evaluation walks the validation set once; the reference feeds the full batch into a model whose hparams say half and so
+walks the set twice: that quirk is not reproduced.  The summaries.jsonl rows carry neither the validation losses nor the long model.
+Not written: the pr_curve-hack plots, boards of gen_images_samples, histograms, graph defs, losses for the training batch at step -1.
+A summary pass changes no variable, Adam moment or noise stream, so a run's checkpoints do not depend on the frequencies.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N` (one process per GPU,
 RCCL gradient exchange = --aggregate_nccl 1 of the reference; the per-GPU batch is batch_size / N like tf.split, base_model.py:523-527).
+Every replica runs the summary passes, the validation losses and the long model's traversal included, without a collective; the chief
+writes the values of its own shard where the reference averages the towers.
 `--dataset synthetic` (not in the reference) feeds seeded uniform video of --synthetic_shape without record files.
 """
 from __future__ import absolute_import, division, print_function
@@ -177,6 +185,44 @@ def get_dataset_class(name, synthetic_shape):
     return datasets.get_dataset_class(name)
 
 
+def long_length_given(hparams_dict, hparams):
+    """Was long_sequence_length set explicitly, in the --dataset_hparams_dict file / the checkpoint's dataset_hparams.json or in the
+    --dataset_hparams string(s)?"""
+    if 'long_sequence_length' in (hparams_dict or {}):
+        return True
+    strings = [] if not hparams else (list(hparams) if isinstance(hparams, (list, tuple)) else [hparams])
+    return any(kv.split('=')[0].strip() == 'long_sequence_length' for text in strings for kv in text.split(','))
+
+
+def long_eval_length(dataset, explicit):
+    """The sequence length of the second, long model of the accumulated evaluation (train.py:136-145), or None when the dataset has no
+    long version: its long_sequence_length where that differs from its sequence_length.  The dataset classes of the reference carry
+    their recipe's pair (softmotion 12 / 30, KTH 20 / 40).  SyntheticVideoDataset carries a constant that has nothing to do with the
+    sequence_length asked for, so it has a long version only when long_sequence_length was given explicitly (long_length_given).
+    Records of a fixed number of frames that is too small for the long version (a dataset written at 12 frames and read with the BAIR
+    class and its default of 30) have none either: the reference's long dataset would deliver nothing."""
+    if isinstance(dataset, SyntheticVideoDataset) and not explicit:
+        return None
+    hp = dataset.hparams
+    long_length = int(getattr(hp, 'long_sequence_length', 0) or 0)
+    if not long_length or long_length == hp.sequence_length:
+        return None
+    frames = getattr(dataset, '_max_sequence_length', 0)          # 0: the length is per example (KTH), short ones are filtered out
+    if frames and not getattr(dataset, 'var_len', False) and (long_length - 1) * (getattr(hp, 'frame_skip', 0) + 1) + 1 > frames:
+        return None
+    return long_length
+
+
+def long_eval_batch(per_gpu):
+    """Per-GPU batch of the long model: half the training batch (train.py:139, batch_size // 2), at least one sequence."""
+    return max(1, per_gpu // 2)
+
+
+def accum_eval_updates(dataset, per_gpu, world):
+    """Updates of one accumulated evaluation: (roughly, up to rounding by the batch size) one traversal of the validation set."""
+    return dataset.num_examples_per_epoch() // (per_gpu * world)
+
+
 def should(step, freq, max_steps, start_step):
     """train.py:232-236."""
     if freq is None:
@@ -262,6 +308,21 @@ def main(argv=None):
     if dist is not None:
         model.engine.attach_process_group(dist)
 
+    # the long model of the accumulated evaluation (train.py:136-145,176-191): test mode, sequence_length = the validation dataset's
+    # long_sequence_length, the training model's variables (share_with = the reference's reuse_variables()), half the per-GPU batch
+    long_model, long_dataset, long_per_gpu, long_iter = None, None, 0, [None]
+    long_length = long_eval_length(val_dataset, long_length_given(dataset_hparams_dict, args.dataset_hparams))
+    if long_length is not None:
+        long_dataset = VideoDataset(args.val_input_dir or args.input_dir, mode='val', seed=args.seed, hparams_dict=dataset_hparams_dict,
+                                    hparams=args.dataset_hparams)
+        long_dataset.set_sequence_length(long_length)
+        long_per_gpu = long_eval_batch(per_gpu)
+        long_model = VideoPredictionModel(mode='test', hparams_dict=dict(hparams_dict, sequence_length=long_length),
+                                          hparams=args.model_hparams, aggregate_nccl=args.aggregate_nccl)
+        long_iter[0] = iter(long_dataset.make_batch(long_per_gpu, device=device, rank=rank, world=world))
+        long_model.build_graph(next(long_iter[0]), device=device, share_with=model)
+        long_iter[0] = None                         # the first evaluation starts at the head of the set
+
     if chief:
         if not os.path.exists(args.output_dir):
             os.makedirs(args.output_dir)
@@ -301,6 +362,16 @@ def main(argv=None):
                 return batch
             summary_iter[0] = None                  # a finite validation set ran out: start over
         raise RuntimeError('the validation dataset delivers no batch')
+
+    def next_long_batch():
+        for _ in range(2):
+            if long_iter[0] is None:
+                long_iter[0] = iter(long_dataset.make_batch(long_per_gpu, device=device, rank=rank, world=world))
+            batch = next(long_iter[0], None)
+            if batch is not None:
+                return batch
+            long_iter[0] = None
+        raise RuntimeError('the long validation dataset delivers no batch')
 
     def writer():
         if event_writer[0] is None:
@@ -370,7 +441,7 @@ def main(argv=None):
             val_inputs = next_summary_batch()        # one validation batch for the three, like the reference's single sess.run
             if do_summary:
                 write_scalars(model.scalar_summary_fn(inputs, info), global_step)
-                write_scalars(model.scalar_summary_fn(val_inputs), global_step, '_1')
+                write_scalars(model.scalar_summary_fn(val_inputs, losses=True), global_step, '_1')
             if do_image:
                 print("recording image summary")
                 write_gifs(model.image_summary_fn(inputs), global_step)
@@ -382,15 +453,20 @@ def main(argv=None):
                     write_gifs(boards, global_step, suffix)
                     write_scalars(values, global_step, suffix)
         if do_accum:
-            model.accum_eval_reset()
-            # traverse (roughly up to rounding based on the batch size) all the validation dataset
-            num_updates = val_dataset.num_examples_per_epoch() // batch_size
-            for update_step in range(num_updates):
-                print('evaluating %d / %d' % (update_step + 1, num_updates))
-                model.accum_eval_update(next_summary_batch())
-            print("recording accum eval summary")
-            write_scalars(model.accum_eval_summary_fn(), global_step, '_1')
-            print("done")
+            # both models (train.py:301-318): reset, then traverse (roughly up to rounding based on the batch size) all the validation
+            # dataset; the main model's tags get the suffix _1, the long model's _2
+            passes = [(model, val_dataset, next_summary_batch, per_gpu, '_1')]
+            if long_model is not None:
+                passes.append((long_model, long_dataset, next_long_batch, long_per_gpu, '_2'))
+            for eval_model, eval_dataset, next_batch, eval_per_gpu, suffix in passes:
+                eval_model.accum_eval_reset()
+                num_updates = accum_eval_updates(eval_dataset, eval_per_gpu, world)
+                for update_step in range(num_updates):
+                    print('evaluating %d / %d' % (update_step + 1, num_updates))
+                    eval_model.accum_eval_update(next_batch())
+                print("recording accum eval summary")
+                write_scalars(eval_model.accum_eval_summary_fn(), global_step, suffix)
+                print("done")
         if do_summary or do_image or do_eval or do_accum:
             model.inputs = inputs
             model.engine.set_images(inputs)                     # back to the training batch, as after the eval summary above

@@ -116,6 +116,38 @@ class _StepProgram(object):
     replay = run
 
 
+def check_shared_variables(store, specs):
+    """Every variable of `specs` (name -> (shape, initialiser)) must be in `store` with that shape: raises for the first that is not."""
+    for name, (shape, _) in specs.items():
+        if name not in store:
+            raise KeyError('shared variable store has no %r' % name)
+        if tuple(store[name].shape) != tuple(shape):
+            raise ValueError('shared variable %r has shape %r, this model needs %r' % (name, tuple(store[name].shape), tuple(shape)))
+
+
+class _SharedVariables(object):
+    """What the networks of a sharing engine see of the other engine's ParamStore: the variables themselves (views of its arenas, no
+    copy), nothing to write to.  The layer objects also ask for gradient views at construction; an inference engine never writes them.
+    grad64 must not register a new float64 accumulator with the owner (ParamGroup.grad64 rebuilds the index tensor of fold64, which the
+    owner's captured train step holds by address): a name the owner has not handed out gets a private tensor."""
+
+    def __init__(self, store):
+        self.store, self.device, self.group_of = store, store.device, store.group_of
+
+    def __getitem__(self, name):
+        return self.store[name]
+
+    def __contains__(self, name):
+        return name in self.store
+
+    def grad(self, name):
+        return self.store.grad(name)
+
+    def grad64(self, name):
+        v = self.store.groups[self.store.group_of[name]]._g64views.get(name)
+        return v if v is not None else torch.zeros(self.store[name].shape, dtype=torch.float64, device=self.device)
+
+
 class SAVPEngine(object):
     """All device state of one SAVP replica: variables, generator unroll (batch 2B: posterior + prior), posterior
     encoder, the two video discriminators; implements one training step and inference."""
@@ -127,8 +159,10 @@ class SAVPEngine(object):
     UNSUPPORTED_WEIGHTS = ('vgg_cdist_weight', 'feature_l2_weight', 'ae_l2_weight')
 
     def __init__(self, hp, image_shape, batch_size, mode='train', values=None, seed=4, device='cuda:0', base_seed=0, rank=0,
-                 cond=(0, 0), lpips_weights=None, pix_distribs=0):
-        """pix_distribs = P: the number of designated pixels of inputs['pix_distribs'] [B, T, H, W, P] (savp_model.py:252-255,408-410,598-621,
+                 cond=(0, 0), lpips_weights=None, pix_distribs=0, store=None):
+        """store: the ParamStore of another engine to look the variables up in instead of creating them (a mode='test' engine only: the
+        long_sequence_length model of scripts/train.py); every name this engine needs must be there with its shape.
+        pix_distribs = P: the number of designated pixels of inputs['pix_distribs'] [B, T, H, W, P] (savp_model.py:252-255,408-410,598-621,
         648-653); 0 (the default) = a model without that input: the key is refused and no buffer, launch or graph node exists for it.
         cond = (n_actions, n_states): the widths of inputs['actions'] [B, T-1, na] / inputs['states'] [B, T, ns] when the dataset
         supplies them (the action / state-conditioned model, savp_model.py:24-26,411-444,655-661; base_model.py:758-762).
@@ -150,9 +184,21 @@ class SAVPEngine(object):
         self.train = mode == 'train'
         check_kernel_size(hp)                  # before the kernel heads are sized from it
         specs = V.variable_specs(hp, image_shape, mode=mode, cond=self.cond)
-        if values is None:
-            values = V.init_variables(specs, seed=seed)
-        self.store = ParamStore(specs, values, self.device)
+        if store is not None:
+            # the reference's reuse_variables(): this engine looks its variables up in another engine's store; it owns its buffers and
+            # weight packs, prepares its weights at every call and never writes the store
+            if values is not None:
+                raise ValueError('values= and store= both given: a sharing engine has no variables of its own to load')
+            if mode == 'train':
+                raise ValueError("store= with mode='train': two optimisers would share one set of moments")
+            check_shared_variables(store, specs)
+            self.store = store
+            store = _SharedVariables(store)
+        else:
+            if values is None:
+                values = V.init_variables(specs, seed=seed)
+            store = self.store = ParamStore(specs, values, self.device)
+        self.net_store = store                 # what this engine's networks are built on
         self.nz = hp.nz
         B = batch_size
         self.T, self.T1 = hp.sequence_length, hp.sequence_length - 1
@@ -161,11 +207,11 @@ class SAVPEngine(object):
         self.P = int(pix_distribs or 0)
         if self.P < 0:
             raise ValueError('pix_distribs = %r: the number of designated pixels' % (pix_distribs,))
-        self.gen = SAVPGenerator(self.store, hp, image_shape, N, train=self.train, cond=self.cond, pix=self.P)
+        self.gen = SAVPGenerator(store, hp, image_shape, N, train=self.train, cond=self.cond, pix=self.P)
         # designated-pixel distributions, staged time-major beside the images (sliced to T1 like every input: savp_model.py:690-691)
         self.pix_tm = torch.empty(self.T1, B, H, W, self.P, device=self.device) if self.P else None
         self.pix_n = (torch.empty(self.T1, N, H, W, self.P, device=self.device) if self.nz else self.pix_tm) if self.P else None
-        self.enc = PosteriorEncoder(self.store, hp, image_shape, B, train=self.train, n_actions=self.na) if self.nz else None
+        self.enc = PosteriorEncoder(store, hp, image_shape, B, train=self.train, n_actions=self.na) if self.nz else None
         # conditioning inputs, time-major; both unrolls (N = 2B: posterior half, prior half) see the same actions / states
         self.actions_tm = torch.zeros(self.T1, B, self.na, device=self.device) if self.na else None
         self.actions_n = (torch.zeros(self.T1, N, self.na, device=self.device) if self.nz else self.actions_tm) if self.na else None
@@ -183,7 +229,7 @@ class SAVPEngine(object):
             raise ValueError('clip_length=%d needs sequence_length >= %d (got %d)' % (hp.clip_length, hp.clip_length + 1, self.T))
         # learned prior (prior_fn, savp_model.py:54-85,717-721): its own encoder + recurrent tail under scope generator/prior
         self.learn_prior = bool(self.nz and hp.learn_prior)
-        self.prior = (PosteriorEncoder(self.store, hp, image_shape, B, train=self.train, prefix='generator/prior/', prior=True,
+        self.prior = (PosteriorEncoder(store, hp, image_shape, B, train=self.train, prefix='generator/prior/', prior=True,
                                        n_actions=self.na)
                       if self.learn_prior else None)
         # (discriminator, loss weight, loss-name infix, operates on the posterior ('_enc') unroll?, clip index keys)
@@ -768,6 +814,18 @@ class SAVPEngine(object):
         if discs and self.dp:
             self._host_op(self.replicas.sync_aux)    # u vectors: bit-identical replicas (parallel.ReplicaGroup.sync_aux)
         # ---- loss bookkeeping (device scalars; base_model.py:733-852) ----------------------------------------------------------
+        # the annealed KL weight is a device scalar here (the graph is replayed with the weight of the current step)
+        info.update(self._loss_info(lb, klw, self.d_scal[2]))
+        return info
+
+    def _loss_info(self, lb, klw, kl_scale):
+        """d_losses / g_losses (name -> (device scalar, weight)) and their weighted sums from the float64 accumulators `lb` of a pass that
+        has just been issued (slots: see __init__) and the encoder's KL.  kl_scale: what g_loss multiplies the KL term by -- the device
+        scalar of the captured step, the host value of an eager pass."""
+        hp, discs = self.hp, self.discs
+        state_w = getattr(hp, 'state_weight', 0) if self.ns else 0
+        tv_w = getattr(hp, 'tv_weight', 0)
+        info = OrderedDict()
         d_losses, g_losses = OrderedDict(), OrderedDict()
         lb = lb.float()                            # the float64 accumulators, rounded once
         for d in discs:
@@ -794,9 +852,78 @@ class SAVPEngine(object):
             g_losses['gen_kl_loss'] = (self.enc.kl.float()[0], klw)
         info['d_losses'], info['g_losses'] = d_losses, g_losses
         info['d_loss'] = sum(l * w for l, w in d_losses.values()) if d_losses else torch.zeros((), device=self.device)
-        # the annealed KL weight is a device scalar here (the graph is replayed with the weight of the current step)
-        info['g_loss'] = sum(l * (self.d_scal[2] if k == 'gen_kl_loss' else w) for k, (l, w) in g_losses.items())
+        info['g_loss'] = sum(l * (kl_scale if k == 'gen_kl_loss' else w) for k, (l, w) in g_losses.items())
         return info
+
+    # -- the losses of a batch without a step (the reference's summary_op on the validation handle, base_model.py:434-446,704-712) -----------
+    LOSS_STREAM = 1 << 16        # _noise_seed stream of eval_losses' draws: 0 is the train step's, 1 + i evaluation sample i's
+
+    def eval_losses(self, noise=None):
+        """The losses of the staged batch, forward only: `info` as train_step returns it (d_losses, g_losses: name -> (device scalar,
+        weight); d_loss, g_loss), nothing synchronised.  One train-mode generator forward (scheduled sampling and KL weight of the current
+        step), the posterior encoder (and the learned prior), then ONE forward per configured discriminator on (real, fake) with the current
+        weights and the current, unassigned u (the u assignment is an UPDATE_OP of the train op only, ops.py:1046-1048); the discriminator
+        and the generator terms read these same logits and features (the reference's g_losses, not g_losses_post: nothing is updated in
+        between) with the clip draws of the step's pre-update call.  gen_tv_loss is taken after the unroll, one launch per time step (a
+        train step takes it inside BPTT, last step first).  Every loss kernel runs without its gradient outputs.
+        Invisible to training like the other summary passes: eager, outside any capture; default draws from a stream of its own (seed, rank,
+        step, LOSS_STREAM); loss accumulators of its own; it writes the staged noise, the activations and the prepared weight packs, which a
+        train step writes before it reads, and no variable, Adam moment, u, counter or gradient."""
+        if not self.train:
+            raise RuntimeError("eval_losses needs a mode='train' engine: losses exist only in train mode (base_model.py:434-446)")
+        hp, B = self.hp, self.B
+        if noise is None:
+            noise = self.default_noise(torch.Generator().manual_seed(self._noise_seed(self.step, stream=self.LOSS_STREAM)))
+        klw = kl_weight(hp, self.step)
+        if getattr(self, 'eval_loss_buf', None) is None:
+            self.eval_loss_buf = torch.zeros_like(self.loss_buf)
+        lb = self.eval_loss_buf
+        lb.zero_()
+        self._stage_noise(noise)
+        self.wait_aux()                # D.prep_weights reads u: order behind a u broadcast still in flight on the side stream
+        K.zero_arena(self.device).reset()
+        self.prep_generator_weights()
+        gen = self.forward_generator(None)
+        gen_enc, gen_prior = (gen[:, :B], gen[:, B:]) if self.nz else (None, gen)
+        prepped = set()
+        for d in self.discs:
+            D, w, slot, is_vae = d['D'], d['w'], d['slot'], d['enc']
+            if id(D) not in prepped:
+                D.prep_weights(update_u=False)
+                prepped.add(id(D))
+            if not w:
+                continue
+            self._d_clips(D, 0, d['kr'], d['kf'], gen_enc if is_vae else gen_prior, 0, B)
+            D.forward()
+            r0, r1 = D.rows(0, B)
+            f0, f1 = D.rows(B, 2 * B)
+            K.gan_loss(D.logits[r0:r1], 1.0, w, hp.gan_loss_type, lb[slot:slot + 1])               # discrim_*_loss real
+            K.gan_loss(D.logits[f0:f1], 0.0, w, hp.gan_loss_type, lb[slot + 1:slot + 2])           # ... fake
+            K.gan_loss(D.logits[f0:f1], 1.0, w, hp.gan_loss_type, lb[slot + 2:slot + 3])           # gen_*_gan_loss
+            wf_cd = hp.vae_gan_feature_cdist_weight if is_vae else hp.gan_feature_cdist_weight
+            wf_l2 = hp.vae_gan_feature_l2_weight if is_vae else hp.gan_feature_l2_weight
+            for L in (D.layers if (wf_cd or wf_l2) else ()):
+                if wf_cd:
+                    K.cosine_distance(L['y'][f0:f1], L['y'][r0:r1], wf_cd, lb[slot + 3:slot + 4])
+                if wf_l2:
+                    K.lp_loss(L['y'][f0:f1], L['y'][r0:r1], wf_l2, lb[slot + 4:slot + 5], p2=True)
+        target = self.images_tm[1:self.T]
+        pred = gen_enc if self.nz else gen_prior
+        if hp.l1_weight:
+            K.lp_loss(pred, target, hp.l1_weight, lb[-2:-1], p2=False)
+        if hp.l2_weight:
+            K.lp_loss(pred, target, hp.l2_weight, lb[-1:], p2=True)
+        state_w = getattr(hp, 'state_weight', 0) if self.ns else 0
+        if state_w:
+            K.lp_loss(self.gen.gen_states.v[:, :B], self.states_tm[1:self.T], state_w, lb[-3:-2], p2=True)
+        tv_w = getattr(hp, 'tv_weight', 0)
+        if tv_w:
+            g = self.gen
+            s1 = 1.0 / (g.T1 * B * (g.H - 1) * g.W)
+            s2 = 1.0 / (g.T1 * B * g.H * (g.W - 1))
+            for t in range(g.T1):
+                K.tv_loss(g.tf_raw.v[t][:B], 2 * g.nk, s1, s2, tv_w, lb[-4:-3])
+        return self._loss_info(lb, klw, klw or 0.0)
 
     # -- inference (scripts/generate.py:166: model.outputs['gen_images']) ------------------------------------------------------
     def generate(self, noise=None, collect_masks=False):
@@ -998,7 +1125,7 @@ class _ParallelPriorEval(object):
         T, T1, nz = eng.T, eng.T1, eng.nz
         self.F = F = T - hp.context_frames
         self.c1 = hp.context_frames - 1
-        self.gen = SAVPGenerator(eng.store, hp, eng.image_shape, N, train=False, cond=eng.cond)
+        self.gen = SAVPGenerator(eng.net_store, hp, eng.image_shape, N, train=False, cond=eng.cond)
         self.images = torch.empty(T, N, H, W, C, device=dev)
         self.zs = torch.zeros(T1, N, nz, device=dev)
         gt = torch.zeros(T1, N, dtype=torch.int32)
@@ -1346,6 +1473,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
             self.discriminator_fn = None
         self.deterministic = not self.hparams.nz
         self.engine = None
+        self._shares = None                    # build_graph(share_with=...): the model whose variables this one reads
 
     def get_default_hparams_dict(self):
         return savp_defaults()
@@ -1356,11 +1484,21 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
             hparams_dict.pop(k, None)
         return super(SAVPVideoPredictionModel, self).parse_hparams(hparams_dict, hparams)
 
-    def build_graph(self, inputs, values=None, seed=4, device='cuda:0'):
+    def build_graph(self, inputs, values=None, seed=4, device='cuda:0', share_with=None):
         """inputs: {'images': [B,T,H,W,C] device tensor, optionally 'actions': [B,T-1,na], 'states': [B,T,ns]} (batch-major like the
         reference's dataset iterator).  As in the reference the input STRUCTURE is fixed here: a model built with actions / states
         expects them in every later batch.  A model created with the pix_distribs opt-in also reads P off inputs['pix_distribs']
-        [B,T,H,W,P] when the batch carries it; every other model refuses the key."""
+        [B,T,H,W,P] when the batch carries it; every other model refuses the key.
+        share_with = a built model (the reference's reuse_variables(), scripts/train.py:136-145): this mode='test' model's engine looks
+        its variables up in that model's ParamStore instead of creating its own -- no copy, so it sees every training step of the other
+        model without a transfer, and its draws follow that model's step counter.  A name it needs that the store lacks, or holds in
+        another shape, raises with the name.  It has its own buffers and weight packs and never writes the store."""
+        store = None
+        if share_with is not None:
+            if getattr(share_with, 'engine', None) is None:
+                raise ValueError('share_with needs a model whose build_graph has run')
+            store = share_with.engine.store
+        self._shares = share_with
         P = 0
         if self.pix_distribs and isinstance(inputs, dict) and inputs.get('pix_distribs') is not None:
             P = int(inputs['pix_distribs'].shape[-1])
@@ -1370,7 +1508,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         images = inputs['images']
         B = images.shape[0]
         self.engine = SAVPEngine(self.hparams, tuple(images.shape[2:]), B, mode=self.mode, values=values, seed=seed,
-                                 device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights, pix_distribs=P)
+                                 device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights, pix_distribs=P, store=store)
         self.saveable_variables = self.engine.store.names()
         self.post_init_ops = []
         self.outputs = {}
@@ -1379,6 +1517,12 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
     @property
     def global_step(self):
         return self.engine.step if self.engine else 0
+
+    def _follow(self):
+        """A model built with share_with has no step of its own: the (seed, rank, step, stream) seeds of its draws take the step of the
+        model that trains the variables."""
+        if self._shares is not None:
+            self.engine.step = self._shares.engine.step
 
     def _refuse(self, inputs):
         """refuse_conditioning_inputs unless this model's engine was built for pix_distribs (the engine then checks every batch itself)."""
@@ -1402,6 +1546,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         if inputs is not None:
             self._refuse(inputs)
             self.inputs = inputs
+        self._follow()
         self.engine.set_images(self.inputs)
         gen = self.engine.generate(noise)
         lo = self.engine.B if self.engine.nz else 0
@@ -1419,6 +1564,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         if inputs is not None:
             self.inputs = inputs
             self.engine.set_images(self.inputs)
+        self._follow()
         self.metrics = self.engine.metrics()
         return self.metrics
 
@@ -1428,6 +1574,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         if inputs is not None:
             self.inputs = inputs
             self.engine.set_images(self.inputs)
+        self._follow()
         self.eval_outputs, self.eval_metrics = self.engine.eval_outputs_and_metrics(
             num_samples or self.eval_num_samples, noises, parallel_iterations=parallel_iterations or self.eval_parallel_iterations,
             num_samples_for_diversity=(self.eval_num_samples_for_diversity if num_samples_for_diversity is None
@@ -1440,23 +1587,30 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
     # generators seeded by (seed, rank, step, stream), never from a stream a later train_step continues.  What it does overwrite is the
     # staged batch, the staged noise and the activations, all of which the next train_step writes before it reads; a caller that passed
     # `inputs` and wants the training batch's conditioning back stages it again (engine.set_images), as scripts/train.py does.
+    # The validation losses come from a forward-only pass (scalar_summary_fn(..., losses=True) -> SAVPEngine.eval_losses); the second,
+    # long_sequence_length model of the accumulated evaluation is a mode='test' model built with build_graph(share_with=...).
     # Not reproduced: the pr_curve-hack plot summaries (they need a patched TensorBoard), boards of gen_images_samples,
-    # the second long_sequence_length model of the accumulated evaluation, histograms and graph defs.
+    # histograms and graph defs.
     SUMMARY_MAX_OUTPUTS = 8                                        # add_gif_summaries(max_outputs=8), tf_utils.py:229-236
 
     def _stage(self, inputs):
         if inputs is not None:
             self._refuse(inputs)
             self.inputs = inputs
+        self._follow()
         self.engine.set_images(self.inputs)
 
-    def scalar_summary_fn(self, inputs=None, info=None):
+    def scalar_summary_fn(self, inputs=None, info=None, losses=False):
         """`summary_op` (base_model.py:704-715): {name: device scalar or number} of every d_losses / g_losses term, d_loss, g_loss,
-        loss = d_loss + g_loss (from `info`, the dict of the train step just run; omitted without one: the losses exist only inside a
-        step here), the metrics_fn results (psnr, mse, ssim, and lpips when its weights are configured) of a prior unroll on `inputs`
-        (default: the current batch) and the 0-d generator outputs ground_truth_sampling_mean(_enc)."""
+        loss = d_loss + g_loss, the metrics_fn results (psnr, mse, ssim, and lpips when its weights are configured) of a prior unroll
+        on `inputs` (default: the current batch) and the 0-d generator outputs ground_truth_sampling_mean(_enc).  The loss entries come
+        from `info`, the dict of the train step just run; without one they are left out, unless losses=True: then a forward-only pass on
+        `inputs` (SAVPEngine.eval_losses: the reference's summary_op run on the validation handle) supplies them."""
         eng = self.engine
         out = OrderedDict()
+        if info is None and losses:
+            self._stage(inputs)
+            info = eng.eval_losses()
         if info is not None:
             for k, (l, _) in list(info['d_losses'].items()) + list(info['g_losses'].items()):
                 out[k] = l

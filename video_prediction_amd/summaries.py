@@ -15,13 +15,13 @@ The first record is Event{wall_time, file_version = "brain.Event:2"}.
 
 Tags.  A tensor or scalar called `name` gets the tag `<scope>/<name>` with scope = name.split('/')[0] (tf_utils._as_name_scope_map opens
 a name scope per first component, so 'gen_images' becomes 'gen_images/gen_images' and 'eval_psnr/min' becomes 'eval_psnr/eval_psnr/min');
-GIFs append '/gif' (gif_summary's op name); validation summaries rename the scope to `scope_1` (add_tag_suffix, reference
-scripts/train.py:18-26).  TensorFlow's outer name scopes (towers) and the `_1`, `_2` suffixes it appends to make op names unique are NOT
+GIFs append '/gif' (gif_summary's op name); validation summaries rename the scope to `scope_1`, the accumulated evaluation of the
+long_sequence_length model to `scope_2` (add_tag_suffix, reference scripts/train.py:18-26,301-318).  The validation scalars include the
+losses (g_loss_1/g_loss, gen_l1_loss_1/gen_l1_loss, ...), taken by a forward-only pass (SAVPEngine.eval_losses).  TensorFlow's outer name scopes (towers) and the `_1`, `_2` suffixes it appends to make op names unique are NOT
 reproduced: a dashboard of this writer shows the same groups with cleaner names.
 
 Out of scope (also DESIGN.md): the `pr_curve`-hack plot summaries of add_plot_and_scalar_summaries (they need a patched TensorBoard; the
-scalar half is written), boards of `gen_images_samples`, the second `long_sequence_length` model of the accumulated evaluation,
-histograms and graph defs.
+scalar half is written), boards of `gen_images_samples`, histograms and graph defs.
 """
 import io as _io
 import os
