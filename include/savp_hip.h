@@ -613,6 +613,9 @@ int savp_dna_apply_multi_bwd(void* stream, const SavpDnaMultiArgs* a);
  *  gates stage : pre [N,HW,2F] -> r,u = sigmoid(IN(pre)); writes u [N,HW,F] and r*h into the candidate conv's input slot
  *  output stage: pre [N,HW,F]  -> c = tanh(IN(pre)); h' = u*h + (1-u)*c written to nout destinations
  *  backward    : out_bwd gives dpre(F), du and dh = u*dh' (overwrites); gates_bwd gives dpre(2F) and dh += d(rh)*r (accumulates)
+ * Three families share SavpGruArgs: these four (one workgroup holds a plane in registers: HW <= 1024, SAVP_EINVAL above), the bare
+ * cell's pointwise savp_convgru_plain_* (any plane) and the chunked two-pass savp_convgru_large_* of gru_large.hip (instance norm,
+ * any plane; the generator uses them for layers whose plane exceeds 1024 pixels).
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct SavpGruArgs {
     int32_t N, HW, F;
@@ -650,6 +653,29 @@ int savp_convgru_plain_gates_fwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_plain_out_fwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_plain_out_bwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_plain_gates_bwd(void* stream, const SavpGruArgs* a);
+/* gru_large.hip: the four INSTANCE-NORM blocks above (same mathematics, same fields of SavpGruArgs, same overwrite / accumulate
+ * contract of dh) for planes of ANY size HW >= 1; savp_convgru_{gates,out}_{fwd,bwd} keep their HW <= 1024 limit.  Each block is two
+ * launches over chunks of pixels: a sums pass (forward: shifted sum / sum of squares of `pre`; backward: sum dz and sum dz*xhat, which
+ * are dbeta and dgamma) that STORES per-chunk float64 partials to `ws`, and an apply pass that folds them in chunk order and writes
+ * its pixels.  No fp32 atomics, no variance as an fp32 difference of means, nothing to clear: equal operands give equal bits, and the
+ * entries allocate nothing (legal in a captured graph).  The statistics are always computed here (no stats_ready shortcut).
+ *  ws, ws_bytes: caller-owned scratch of at least savp_convgru_large_ws_bytes(N, HW, F) bytes, 8-byte aligned, contents arbitrary;
+ *                written and read by the one call only, so one buffer may serve every call on a stream.
+ *  savp_convgru_large_chunk(N, HW): the pixels per workgroup the launchers use (0 for N or HW < 1); host-side arithmetic.
+ * SAVP_EINVAL, without a launch: F % 4 != 0, N or HW < 1 (N > 65535), a null pointer among those the entry uses, a base pointer or
+ * view stride that breaks 16-byte access (pre, u, du, dpre, gamma, beta, mean, rstd and every view base 16-byte aligned; sn and sp
+ * multiples of 4 floats), ws null, misaligned or shorter than the query's answer. */
+typedef struct SavpGruLargeArgs {
+    SavpGruArgs g;
+    void* ws;
+    int64_t ws_bytes;
+} SavpGruLargeArgs;
+int32_t savp_convgru_large_chunk(int32_t N, int32_t HW);
+int64_t savp_convgru_large_ws_bytes(int32_t N, int32_t HW, int32_t F);
+int savp_convgru_large_gates_fwd(void* stream, const SavpGruLargeArgs* a);
+int savp_convgru_large_out_fwd(void* stream, const SavpGruLargeArgs* a);
+int savp_convgru_large_out_bwd(void* stream, const SavpGruLargeArgs* a);
+int savp_convgru_large_gates_bwd(void* stream, const SavpGruLargeArgs* a);
 
 /* uint8 frames [B, T, frame] -> float32 time-major [T, B, frame] * (1/255): tf.image.convert_image_dtype (base_dataset.py:187)
  * + transpose_batch_time (tf_utils.py:118-122) for batches delivered by libsavp_io.so (include/savp_io.h); frame % 4 == 0 */

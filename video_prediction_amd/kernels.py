@@ -1674,6 +1674,80 @@ def convgru_plain_gates_bwd(pre, h, du, drh, dpre, dh):
     lib.check(_L().savp_convgru_plain_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_gates_bwd')
 
 
+# the instance-norm cell on planes of any size (csrc/gru_large.hip): chunked sums pass + apply pass, per-chunk float64 partials in `ws`
+GRU_SMALL_MAX_HW = 1024           # MAXPPT x NT of csrc/gru.hip: convgru_* above refuse more, convgru_large_* take any plane
+GRU_LARGE_MAX_CHUNKS = 64         # GL_MAX_CHUNKS
+GRU_LARGE_PARTIALS = 4            # GL_K: float64 partials per channel of F and chunk
+
+
+def convgru_large_chunk(N, HW):
+    """Pixels per workgroup of the convgru_large_* launchers (savp_convgru_large_chunk restated, so that it is known without the library):
+    about 512 workgroups per launch, between 32 and 256 pixels, and at most GRU_LARGE_MAX_CHUNKS chunks per plane."""
+    if N < 1 or HW < 1:
+        return 0
+    c = min(max((N * HW + 511) // 512, 32), 256)
+    if (HW + c - 1) // c > GRU_LARGE_MAX_CHUNKS:
+        c = (HW + GRU_LARGE_MAX_CHUNKS - 1) // GRU_LARGE_MAX_CHUNKS
+    return c
+
+
+def convgru_large_ws_bytes(N, HW, F):
+    """Bytes of the float64 workspace [N, chunks, 4, F] one convgru_large_* call needs (savp_convgru_large_ws_bytes restated)."""
+    c = convgru_large_chunk(N, HW)
+    if not c or F < 1:
+        return 0
+    return N * ((HW + c - 1) // c) * GRU_LARGE_PARTIALS * F * 8
+
+
+def convgru_large_ws(device, N, HW, F):
+    """A workspace for the convgru_large_* calls of one layer: allocated once by the caller, its contents never matter between calls."""
+    return torch.empty(convgru_large_ws_bytes(N, HW, F) // 8, dtype=torch.float64, device=device)
+
+
+def _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, F, eps):
+    a = lib.SavpGruLargeArgs()
+    a.g = _gru_args(pre, h, gamma, beta, mean, rstd, F, eps)
+    if ws is not None:
+        lib.require_stats(ws)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    return a
+
+
+def convgru_large_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, ws, eps=1e-6):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
+    a.g.u, a.g.rh = _p(u), view(rh)
+    lib.check(_L().savp_convgru_large_gates_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_gates_fwd')
+
+
+def convgru_large_out_fwd(pre, h, gamma, beta, mean, rstd, u, outs, ws, eps=1e-6):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
+    a.g.u = _p(u)
+    a.g.nout = len(outs)
+    _set_views(a.g.out, outs)
+    lib.check(_L().savp_convgru_large_out_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_out_fwd')
+
+
+def convgru_large_out_bwd(pre, h, gamma, beta, mean, rstd, u, dys, dpre, du, dh, dgamma, dbeta, ws, eps=1e-6):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
+    a.g.u = _p(u)
+    a.g.ndy = len(dys)
+    _set_views(a.g.dy, dys)
+    a.g.dpre, a.g.du, a.g.dh = _p(dpre), _p(du), view(dh)
+    acc = _Acc64(dgamma, dbeta)
+    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
+    lib.check(_L().savp_convgru_large_out_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_out_bwd')
+    acc.finish()
+
+
+def convgru_large_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma, dbeta, ws, eps=1e-6):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
+    a.g.du, a.g.drh, a.g.dpre, a.g.dh = _p(du), view(drh), _p(dpre), view(dh)
+    acc = _Acc64(dgamma, dbeta)
+    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
+    lib.check(_L().savp_convgru_large_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_gates_bwd')
+    acc.finish()
+
+
 GAN_TYPES = {'LSGAN': 0, 'GAN': 1, 'SNGAN': 2}
 
 

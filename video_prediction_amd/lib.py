@@ -156,6 +156,8 @@ def _declare(lib):
     _sig(lib, 'savp_tiled_z_workspace_bytes', [c_i64, c_i32], restype=c_i64)
     _sig(lib, 'savp_eval_fold_ws_floats', [c_i32, c_i32, c_i32, c_i32], restype=c_i64)
     _sig(lib, 'savp_jpeg_workspace_bytes', [P(SavpJpegArgs)], restype=c_i64)
+    _sig(lib, 'savp_convgru_large_chunk', [c_i32, c_i32])
+    _sig(lib, 'savp_convgru_large_ws_bytes', [c_i32, c_i32, c_i32], restype=c_i64)
     for name, argtypes in _EXTRA_SIGS.items():
         _sig(lib, name, argtypes)
 
@@ -471,6 +473,14 @@ class SavpGruArgs(ctypes.Structure):
 for _n in ('savp_convgru_gates_fwd', 'savp_convgru_out_fwd', 'savp_convgru_out_bwd', 'savp_convgru_gates_bwd',
            'savp_convgru_plain_gates_fwd', 'savp_convgru_plain_out_fwd', 'savp_convgru_plain_out_bwd', 'savp_convgru_plain_gates_bwd'):
     register(_n, [c_vp, ctypes.POINTER(SavpGruArgs)])
+
+
+class SavpGruLargeArgs(ctypes.Structure):
+    _fields_ = [('g', SavpGruArgs), ('ws', c_vp), ('ws_bytes', c_i64)]
+
+
+for _n in ('savp_convgru_large_gates_fwd', 'savp_convgru_large_out_fwd', 'savp_convgru_large_out_bwd', 'savp_convgru_large_gates_bwd'):
+    register(_n, [c_vp, ctypes.POINTER(SavpGruLargeArgs)])
 register('savp_gan_loss', [c_vp, c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_i32])
 register('savp_fold_f64', [c_vp, c_vp, c_i64, c_vp, c_vp])
 register('savp_tv_loss', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp])
