@@ -371,6 +371,47 @@ int savp_adam(void* stream, int64_t n, float* p, const float* g, float* m, float
               float eps, float gscale, const float* lr_t_dev);   /* lr_t_dev != NULL: lr_t is read from device memory
                                                                     (hipGraph replays of the step with a changing rate) */
 
+/* health.hip: the opt-in guard of a training run (SAVPEngine(guard=True) / SAVP_GUARD=1).
+ * savp_arena_health: what is in one flat fp32 arena x of n floats (an optimiser group's gradient arena), per variable and in total.
+ *  segments : device int64 [S][2] = (offset, length) of each variable's slot in x, in floats; offsets are multiples of 4, lengths
+ *             arbitrary (>= 1).  The zero padding between slots belongs to no segment and is never read.
+ *  items    : device int64 [n_items][3] = (segment, start, count): `count` <= savp_arena_health_chunk() floats of that segment from its
+ *             element `start` (a multiple of 4) on; in segment order, and within a segment in order of `start`, every element once.
+ *  sumsq[S] (float64, the FINITE elements' squares; the square of an fp32 is exact in float64), nonfinite[S] (NaN, +Inf, -Inf),
+ *  total_sumsq, total_nonfinite, ok = (total_nonfinite == 0), and counters[3] the call maintains itself: [0] skipped += 1 when not ok;
+ *  [1] consecutive = 0 when ok, += 1 otherwise; [2] first_bad_segment = the lowest segment with a non-finite element, -1 when ok.
+ *  counters[0..1] are running state: whoever owns them sets them to 0 once.  Everything else is written whole by every call.
+ * Two launches: one workgroup per item (float4 loads, a scalar tail of 1..3 floats) STORES its (float64, int32) partial to ws[item]; then
+ * ONE workgroup folds the items in list order, the segments in order, and writes totals, flag and counters.  No atomics, no completion
+ * counter, nothing to clear, no allocation: equal input gives equal bits and both launches are legal in a captured graph.
+ *  ws, ws_bytes: caller-owned scratch of at least savp_arena_health_ws_bytes(n_items) bytes, 16-byte aligned, contents arbitrary.
+ * An item that points outside its list's segments or outside x is counted as empty, never read.
+ * SAVP_EINVAL, without a launch: a null pointer, S < 1, n_items < 1 (an empty item list), n < 1, x or ws not 16-byte aligned (the other
+ * 8-byte quantities 8), ws shorter than the query's answer. */
+typedef struct SavpHealthArgs {
+    const float* x;
+    int64_t n;
+    int64_t S;
+    int64_t n_items;
+    const int64_t* segments;
+    const int64_t* items;
+    double* sumsq;
+    int32_t* nonfinite;
+    double* total_sumsq;
+    int32_t* total_nonfinite;
+    int32_t* ok;
+    int32_t* counters;
+    void* ws;
+    int64_t ws_bytes;
+} SavpHealthArgs;
+int32_t savp_arena_health_chunk(void);                  /* floats per item at the most; host-side arithmetic */
+int64_t savp_arena_health_ws_bytes(int64_t n_items);    /* 0 for n_items < 1 */
+int savp_arena_health(void* stream, const SavpHealthArgs* a);
+/* savp_adam behind the flag savp_arena_health wrote (device memory): *ok == 0 -> no thread stores anything, p, m and v keep their bits;
+ * otherwise exactly savp_adam's update (one shared implementation of the arithmetic, csrc/adam_update.h).  Same refusals, and ok null. */
+int savp_adam_guarded(void* stream, int64_t n, float* p, const float* g, float* m, float* v, float lr_t, float beta1, float beta2,
+                      float eps, float gscale, const float* lr_t_dev, const int32_t* ok);
+
 /* ------------------------------------------------------------------------------------------------------------
  * CDNA head + mask compositing (cdna_composite.hip): savp_model.py:551-559, 893-923, 634-646.
  * ------------------------------------------------------------------------------------------------------------ */

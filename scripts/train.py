@@ -32,6 +32,11 @@ Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N` (on
 RCCL gradient exchange = --aggregate_nccl 1 of the reference; the per-GPU batch is batch_size / N like tf.split, base_model.py:523-527).
 Every replica runs the summary passes, the validation losses and the long model's traversal included, without a collective; the chief
 writes the values of its own shard where the reference averages the towers.
+SAVP_GUARD=1 (no flag: the flag set is the reference's) trains with the engine's guard: an optimiser group whose gradient holds a NaN or
+Inf skips its Adam update.  The progress block then adds both groups' gradient norms and skipped-step counts, the scalar summaries gain
+grad_norm_d / grad_norm_g / skipped_steps_d / skipped_steps_g (summaries.jsonl and the event file), and when a group has skipped
+SAVP_GUARD_MAX_SKIPS (default 10) steps in a row at a progress check the run prints that group's per-variable report, worst first, saves
+the still-finite state as model-<global_step> and exits with a non-zero status.  Without SAVP_GUARD output and files are unchanged.
 `--dataset synthetic` (not in the reference) feeds seeded uniform video of --synthetic_shape without record files.
 """
 from __future__ import absolute_import, division, print_function
@@ -345,7 +350,19 @@ def main(argv=None):
         out = {'d_loss': float(info['d_loss']), 'g_loss': float(info['g_loss'])}
         for k, (l, w) in list(info['d_losses'].items()) + list(info['g_losses'].items()):
             out[k] = float(l)
+        out.update((k, float(v)) for k, v in model.health_scalars(info).items())      # the guard's four (SAVP_GUARD=1), else nothing
         return out
+
+    GROUP_NAMES = {'d': 'discriminator', 'g': 'generator'}
+    guard_max_skips = int(os.environ.get('SAVP_GUARD_MAX_SKIPS', '10'))
+
+    def guard_tripped(info):
+        """The group ('d' or 'g') whose last `guard_max_skips` Adam updates were all skipped, or None (synchronises: progress checks only)."""
+        health = (info or {}).get('health') or {}
+        for grp in ('d', 'g'):
+            if 'consecutive_' + grp in health and int(health['consecutive_' + grp]) >= guard_max_skips:
+                return grp
+        return None
 
     # TensorBoard summaries (video_prediction_amd/summaries.py).  Every replica runs the summary passes (they touch no variable and no
     # collective, so the replicas stay bit-identical); only the chief opens the event file, at its first write.  The validation batches
@@ -494,6 +511,32 @@ def main(argv=None):
                 for name, (loss, _) in info['g_losses'].items():
                     print("  ", name, float(loss))
                 print("learning_rate", info["learning_rate"])
+                health = info.get('health')
+                if health:
+                    print("grad_norm", "  ".join("%s %g (skipped %d)" % (GROUP_NAMES[grp], float(health['grad_norm_' + grp]),
+                                                                          int(health['skipped_' + grp]))
+                                                 for grp in ('d', 'g') if 'grad_norm_' + grp in health))
+        if step >= 0 and should(step, args.progress_freq, max_steps, start_step):
+            # every replica sees the same reduced gradient, hence the same counters: all of them leave together
+            bad = guard_tripped(info)
+            if bad is not None:
+                reason = ('stopping at global step %d: the %s gradient was non-finite in %d consecutive steps (SAVP_GUARD_MAX_SKIPS=%d); '
+                          'its updates were skipped' % (model.global_step, GROUP_NAMES[bad], int(info['health']['consecutive_' + bad]),
+                                                        guard_max_skips))
+                if chief:
+                    print("gradient report of the %s group, worst first (variable, norm, non-finite elements)" % GROUP_NAMES[bad])
+                    for name, norm, count in sorted(model.engine.health_report(bad), key=lambda r: (-r[2], -r[1])):
+                        print("   %s  %g  %d" % (name, norm, count))
+                    print("saving model to", args.output_dir)
+                    model.save(os.path.join(args.output_dir, "model-%d" % model.global_step))
+                    prune_checkpoints(args.output_dir)
+                    print("done")
+                    summaries.close()
+                    if event_writer[0] is not None:
+                        event_writer[0].close()
+                if dist is not None:
+                    dist.destroy_process_group()
+                raise SystemExit(reason)
         if chief and step >= 0 and should(step, args.save_freq, max_steps, start_step):
             print("saving model to", args.output_dir)
             model.save(os.path.join(args.output_dir, "model-%d" % model.global_step))

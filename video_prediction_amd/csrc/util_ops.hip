@@ -16,6 +16,7 @@
 #include "savp_hip.h"
 #include "zero_fill.h"
 #include "opts.h"
+#include "adam_update.h"
 
 #define NT 256
 
@@ -434,36 +435,11 @@ extern "C" int savp_fill_view(void* stream, SavpView out, int64_t R, int32_t HW,
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// TF Adam: lr_t = lr*sqrt(1-b2^t)/(1-b1^t) is computed on the host and passed in;
-//   m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g^2 ; p -= lr_t * m / (sqrt(v) + eps)       (epsilon outside the sqrt)
-// gscale multiplies the gradient first (1/world_size after a sum all-reduce).
+// TF Adam on a flat arena: the arithmetic lives in adam_update.h, shared with savp_adam_guarded (health.hip)
 __global__ void adam_kernel(long long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, float lr_host, float b1, float b2, float eps, float gscale, const float* lr_dev) {
-    const float lr_t = lr_dev ? *lr_dev : lr_host;
-    long long n4 = n / 4;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-#define ADAM1(f)                                       \
-    {                                                  \
-        float gr = gg.f * gscale;                      \
-        mm.f = b1 * mm.f + (1.f - b1) * gr;            \
-        vv.f = b2 * vv.f + (1.f - b2) * gr * gr;       \
-        pp.f -= lr_t * mm.f / (sqrtf(vv.f) + eps);     \
-    }
-        ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
-#undef ADAM1
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-    }
-    for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float gr = g[i] * gscale;
-        float mi = b1 * m[i] + (1.f - b1) * gr;
-        float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-        m[i] = mi; v[i] = vi;
-        p[i] -= lr_t * mi / (sqrtf(vi) + eps);
-    }
+    savp_adam_update(n, p, g, m, v, lr_host, b1, b2, eps, gscale, lr_dev, blockIdx.x * (long long)blockDim.x + threadIdx.x,
+                     (long long)gridDim.x * blockDim.x);
 }
 
 extern "C" int savp_adam(void* stream, int64_t n, float* p, const float* g, float* m, float* v, float lr_t, float beta1,

@@ -76,6 +76,7 @@ class ParamGroup(object):
         # order), fold64() rounds to fp32 once.  Only the variables somebody asked for (grad64) are folded.
         self.g64 = torch.zeros(self.arena.size, device=device, dtype=torch.float64)
         self._g64views, self._g64idx, self._g64names = {}, None, []
+        self.health_state = None       # enable_health(): the guard's buffers
 
     def param(self, name):
         return self.arena[name]
@@ -116,8 +117,48 @@ class ParamGroup(object):
         self.t += 1
         return lr * math.sqrt(1.0 - beta2 ** self.t) / (1.0 - beta1 ** self.t)
 
-    def adam_apply(self, lr_t, beta1, beta2, gscale=1.0, eps=1e-8, lr_t_dev=None):
-        K.adam(self.p, self.g, self.m, self.v, lr_t, beta1, beta2, eps=eps, gscale=gscale, lr_t_dev=lr_t_dev)
+    def adam_apply(self, lr_t, beta1, beta2, gscale=1.0, eps=1e-8, lr_t_dev=None, ok=None):
+        """ok: the device flag health() wrote -- the update then runs behind it (savp_adam_guarded): a flag of 0 leaves the variables and
+        both moments untouched.  The step count `t` is the host's and advances either way (next_lr_t): the bias correction counts
+        attempted steps."""
+        if ok is not None:
+            K.adam_guarded(self.p, self.g, self.m, self.v, lr_t, beta1, beta2, ok, eps=eps, gscale=gscale, lr_t_dev=lr_t_dev)
+        else:
+            K.adam(self.p, self.g, self.m, self.v, lr_t, beta1, beta2, eps=eps, gscale=gscale, lr_t_dev=lr_t_dev)
+
+    # -- the guard's view of the gradient arena (csrc/health.hip) ------------------------------------------------------------------
+    def enable_health(self):
+        """Build the segment table (one (offset, length) per variable: the padding between slots belongs to none) and the work-list of
+        savp_arena_health once, and allocate its outputs and scratch.  Nothing of this exists for a group that never asks."""
+        if self.health_state is not None:
+            return
+        dev = self.g.device
+        segs = [(off, n) for off, n, _ in self.arena.offsets.values()]
+        items = K.arena_health_worklist(segs)
+        if not items:
+            raise ValueError('an optimiser group without variables has no gradient to watch')
+        self.health_names = list(self.arena.offsets.keys())
+        self.health_segments = torch.tensor(segs, dtype=torch.int64).reshape(-1, 2).to(dev)
+        self.health_items = torch.tensor(items, dtype=torch.int64).reshape(-1, 3).to(dev)
+        self.health_sumsq = torch.zeros(len(segs), dtype=torch.float64, device=dev)
+        self.health_nonfinite = torch.zeros(len(segs), dtype=torch.int32, device=dev)
+        self.health_total = torch.zeros(1, dtype=torch.float64, device=dev)
+        # int32 [5]: total_nonfinite, ok, skipped, consecutive, first_bad_segment (skipped / consecutive run on from 0)
+        self.health_state = torch.zeros(5, dtype=torch.int32, device=dev)
+        self.health_ws = torch.empty(K.arena_health_ws_bytes(len(items)) // 8, dtype=torch.float64, device=dev)
+
+    def health(self):
+        """Launch the two passes over the CURRENT gradient arena on the current stream (after the last fold64(), and after the gradient
+        exchange where there is one); returns the device flag `ok` (int32 [1]) for adam_apply(ok=...)."""
+        K.arena_health(self.g, self.health_segments, self.health_items, self.health_sumsq, self.health_nonfinite, self.health_total,
+                       self.health_state, self.health_ws)
+        return self.health_state[1:2]
+
+    def health_table(self):
+        """[(variable name, gradient norm, non-finite count)] of the last health() as host values (synchronises)."""
+        norm = self.health_sumsq.sqrt().cpu().tolist()
+        bad = self.health_nonfinite.cpu().tolist()
+        return [(n, norm[i], int(bad[i])) for i, n in enumerate(self.health_names)]
 
     def adam_step(self, lr, beta1, beta2, gscale=1.0, eps=1e-8):
         self.adam_apply(self.next_lr_t(lr, beta1, beta2), beta1, beta2, gscale=gscale, eps=eps)

@@ -1116,6 +1116,57 @@ def adam(p, g, m, v, lr_t, beta1, beta2, eps=1e-8, gscale=1.0, lr_t_dev=None):
                              float(eps), float(gscale), _p(lr_t_dev) if lr_t_dev is not None else None), 'savp_adam')
 
 
+def adam_guarded(p, g, m, v, lr_t, beta1, beta2, ok, eps=1e-8, gscale=1.0, lr_t_dev=None):
+    """adam() behind the device flag `ok` (int32, 1 element; arena_health writes it): 0 leaves p, m and v untouched."""
+    if ok is None or ok.dtype != torch.int32 or not ok.is_cuda:
+        raise RuntimeError('adam_guarded needs the int32 device flag arena_health wrote')
+    lib.check(_L().savp_adam_guarded(lib.stream(), p.numel(), _p(p), _p(g), _p(m), _p(v), float(lr_t), float(beta1), float(beta2),
+                                     float(eps), float(gscale), _p(lr_t_dev) if lr_t_dev is not None else None, _p(ok)),
+              'savp_adam_guarded')
+
+
+# the guard's reduction over a gradient arena (csrc/health.hip)
+ARENA_HEALTH_CHUNK = 8192         # HL_CHUNK: floats per work-list item at the most
+ARENA_HEALTH_PARTIAL_BYTES = 16   # sizeof(HealthPartial): (float64, int32, pad) per item
+ARENA_HEALTH_STAGE = 3072         # HL_STAGE: lists of up to this many items are folded from LDS, longer ones from global memory
+
+
+def arena_health_chunk():
+    """savp_arena_health_chunk restated, so that the work-list can be built (and tested) without the library."""
+    return ARENA_HEALTH_CHUNK
+
+
+def arena_health_ws_bytes(n_items):
+    return max(0, int(n_items)) * ARENA_HEALTH_PARTIAL_BYTES
+
+
+def arena_health_worklist(segments, chunk=None):
+    """segments: [(offset, length)] of an arena's variables -> [(segment, start, count)]: every segment cut into pieces of `chunk` floats
+    (the last one shorter), in segment order; `start` counts from the segment's first element."""
+    chunk = chunk or ARENA_HEALTH_CHUNK
+    items = []
+    for s, (_, n) in enumerate(segments):
+        for start in range(0, n, chunk):
+            items.append((s, start, min(chunk, n - start)))
+    return items
+
+
+def arena_health(x, segments, items, sumsq, nonfinite, total_sumsq, state, ws):
+    """savp_arena_health (include/savp_hip.h).  x: the flat fp32 arena; segments int64 [S, 2] and items int64 [n_items, 3] on the device;
+    sumsq float64 [S], nonfinite int32 [S], total_sumsq float64 [1]; state int32 [5] = (total_nonfinite, ok, skipped, consecutive,
+    first_bad_segment), of which the call keeps skipped and consecutive running; ws: arena_health_ws_bytes(n_items) bytes of scratch."""
+    lib.require_device(x)
+    a = lib.SavpHealthArgs()
+    a.x, a.n = x.data_ptr(), x.numel()
+    a.S, a.n_items = segments.shape[0], items.shape[0]
+    a.segments, a.items = segments.data_ptr(), items.data_ptr()
+    a.sumsq, a.nonfinite, a.total_sumsq = sumsq.data_ptr(), nonfinite.data_ptr(), total_sumsq.data_ptr()
+    base = state.data_ptr()
+    a.total_nonfinite, a.ok, a.counters = base, base + 4, base + 8
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    lib.check(_L().savp_arena_health(lib.stream(), ctypes.byref(a)), 'savp_arena_health')
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # cdna / composite
 # ---------------------------------------------------------------------------------------------------------------

@@ -158,6 +158,8 @@ def _declare(lib):
     _sig(lib, 'savp_jpeg_workspace_bytes', [P(SavpJpegArgs)], restype=c_i64)
     _sig(lib, 'savp_convgru_large_chunk', [c_i32, c_i32])
     _sig(lib, 'savp_convgru_large_ws_bytes', [c_i32, c_i32, c_i32], restype=c_i64)
+    _sig(lib, 'savp_arena_health_chunk', [])
+    _sig(lib, 'savp_arena_health_ws_bytes', [c_i64], restype=c_i64)
     for name, argtypes in _EXTRA_SIGS.items():
         _sig(lib, name, argtypes)
 
@@ -366,6 +368,16 @@ register('savp_lpips_diversity_add', [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i
 register('savp_summary_board_u8', [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp])
 register('savp_flow_to_rgb', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp])
 register('savp_adam', [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp])
+
+
+class SavpHealthArgs(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('n', c_i64), ('S', c_i64), ('n_items', c_i64), ('segments', c_vp), ('items', c_vp),
+                ('sumsq', c_vp), ('nonfinite', c_vp), ('total_sumsq', c_vp), ('total_nonfinite', c_vp), ('ok', c_vp), ('counters', c_vp),
+                ('ws', c_vp), ('ws_bytes', c_i64)]
+
+
+register('savp_arena_health', [c_vp, ctypes.POINTER(SavpHealthArgs)])
+register('savp_adam_guarded', [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp])
 register('savp_cdna_kernels_fwd', [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])
 register('savp_cdna_kernels_bwd', [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32])
 register('savp_cdna_apply_fwd', [c_vp, ctypes.POINTER(SavpCdnaArgs)])

@@ -159,7 +159,7 @@ class SAVPEngine(object):
     UNSUPPORTED_WEIGHTS = ('vgg_cdist_weight', 'feature_l2_weight', 'ae_l2_weight')
 
     def __init__(self, hp, image_shape, batch_size, mode='train', values=None, seed=4, device='cuda:0', base_seed=0, rank=0,
-                 cond=(0, 0), lpips_weights=None, pix_distribs=0, store=None):
+                 cond=(0, 0), lpips_weights=None, pix_distribs=0, store=None, guard=None):
         """store: the ParamStore of another engine to look the variables up in instead of creating them (a mode='test' engine only: the
         long_sequence_length model of scripts/train.py); every name this engine needs must be there with its shape.
         pix_distribs = P: the number of designated pixels of inputs['pix_distribs'] [B, T, H, W, P] (savp_model.py:252-255,408-410,598-621,
@@ -167,7 +167,10 @@ class SAVPEngine(object):
         cond = (n_actions, n_states): the widths of inputs['actions'] [B, T-1, na] / inputs['states'] [B, T, ns] when the dataset
         supplies them (the action / state-conditioned model, savp_model.py:24-26,411-444,655-661; base_model.py:758-762).
         lpips_weights: path of the LPIPS network's .npz (video_prediction_amd.lpips; default: the SAVP_LPIPS_WEIGHTS environment
-        variable); without one the lpips metric and eval_diversity are not produced."""
+        variable); without one the lpips metric and eval_diversity are not produced.
+        guard: skip an optimiser group's Adam update when its gradient holds a non-finite value, and report gradient norms (default: the
+        SAVP_GUARD environment variable, '1' = on; off otherwise).  mode='train' only: an inference engine has no gradient and ignores it.
+        Off, the step has no buffer, launch or graph node for it.  See guard_enabled() and _guarded_adam()."""
         self.hp, self.mode, self.B = hp, mode, batch_size
         bad = [k for k in self.UNSUPPORTED_WEIGHTS if getattr(hp, k, 0)]
         if bad and mode == 'train':
@@ -285,6 +288,10 @@ class SAVPEngine(object):
         self.eager_steps = 0
         self.infer_graph = os.environ.get('SAVP_INFER_GRAPH', '1') == '1' and self.device.type == 'cuda'
         self.gen_graph, self.gen_graph_out, self.gen_eager = None, None, 0
+        self.guard = guard_enabled(guard, mode)
+        if self.guard:
+            for grp in ('d', 'g') if self.discs else ('g',):
+                self.store.groups[grp].enable_health()
         self.lpips, self._lp = None, None
         path = _lpips.configured_path(lpips_weights)
         if path:
@@ -723,7 +730,7 @@ class SAVPEngine(object):
             self.gen.gen.g.zero_()
             if not hp.joint_gan_optimization:
                 self._allreduce('d')
-                store.groups['d'].adam_apply(0.0, hp.beta1, hp.beta2, gscale=1.0 / self.world, lr_t_dev=self.d_scal[0:1])
+                self._guarded_adam('d', self.d_scal[0:1], info)
             # joint_gan_optimization (base_model.py:498-505): no control dependency on the D update and no replace_read_ops, i.e. the
             # generator loss is taken against the PRE-update discriminator; D's Adam is applied after the generator step below
             # (its gradient exchange then overlaps the whole generator step)
@@ -805,10 +812,10 @@ class SAVPEngine(object):
         if return_grads:
             info['g_grads'] = {n: store.grad(n).clone() for n in store.names() if store.group_of[n] == 'g'}
         self._allreduce('g')
-        store.groups['g'].adam_apply(0.0, hp.beta1, hp.beta2, gscale=1.0 / self.world, lr_t_dev=self.d_scal[1:2])
+        self._guarded_adam('g', self.d_scal[1:2], info)
         if discs and hp.joint_gan_optimization:
             self._allreduce('d')
-            store.groups['d'].adam_apply(0.0, hp.beta1, hp.beta2, gscale=1.0 / self.world, lr_t_dev=self.d_scal[0:1])
+            self._guarded_adam('d', self.d_scal[0:1], info)
         for D in {id(d['D']): d['D'] for d in discs}.values():
             D.commit_u()
         if discs and self.dp:
@@ -817,6 +824,35 @@ class SAVPEngine(object):
         # the annealed KL weight is a device scalar here (the graph is replayed with the weight of the current step)
         info.update(self._loss_info(lb, klw, self.d_scal[2]))
         return info
+
+    def _guarded_adam(self, group, lr_t_dev, info):
+        """The Adam update of one optimiser group at the end of its half of the step: its gradients are final (the last fold64() is behind,
+        and with replicas the group's all-reduce has been joined, so the arena holds the SUM over replicas and every rank sees the same
+        numbers and takes the same decision).  Guard off: the plain update.  Guard on: savp_arena_health over the gradient arena on this
+        stream, then the update behind its flag; D and G each have their own.  A skipped update leaves the group's variables and both
+        moments as they were.  It does NOT hold back the host's Adam step count (ParamGroup.t: the host never learns the outcome, so
+        the bias correction counts attempted steps) nor the spectral-norm u vectors (they follow from the weights alone, which stay
+        finite).  info['health'] gets the group's device scalars."""
+        hp, grp = self.hp, self.store.groups[group]
+        if not self.guard:
+            grp.adam_apply(0.0, hp.beta1, hp.beta2, gscale=1.0 / self.world, lr_t_dev=lr_t_dev)
+            return
+        ok = grp.health()
+        grp.adam_apply(0.0, hp.beta1, hp.beta2, gscale=1.0 / self.world, lr_t_dev=lr_t_dev, ok=ok)
+        h = info.setdefault('health', OrderedDict())
+        st = grp.health_state
+        h['grad_norm_' + group] = grp.health_total[0].sqrt() / self.world      # the norm of the gradient Adam would apply (gscale = 1 / world)
+        h['nonfinite_' + group], h['skipped_' + group], h['consecutive_' + group] = st[0], st[2], st[3]
+
+    def health_report(self, group=None):
+        """The per-variable table of the last guarded step as host values: [(variable name, gradient norm / world, non-finite count)] of
+        `group` ('d' or 'g'; default both, D first).  Synchronises: for the moment something went wrong."""
+        if not self.guard:
+            raise RuntimeError('health_report() needs an engine built with guard=True (or SAVP_GUARD=1)')
+        out = []
+        for grp in ([group] if group else [k for k in ('d', 'g') if self.store.groups[k].health_state is not None]):
+            out += [(n, norm / self.world, bad) for n, norm, bad in self.store.groups[grp].health_table()]
+        return out
 
     def _loss_info(self, lb, klw, kl_scale):
         """d_losses / g_losses (name -> (device scalar, weight)) and their weighted sums from the float64 accumulators `lb` of a pass that
@@ -1298,6 +1334,14 @@ class _ParallelPriorEval(object):
 _ENGINES = {}
 
 
+def guard_enabled(flag=None, mode='train'):
+    """The guard switch of SAVPEngine / the model classes: an explicit flag, else the SAVP_GUARD environment variable ('1' = on); only a
+    mode='train' model has an optimiser to guard, any other mode ignores the switch."""
+    if flag is None:
+        flag = os.environ.get('SAVP_GUARD', '0') == '1'
+    return bool(flag) and mode == 'train'
+
+
 def refuse_conditioning_inputs(inputs):
     """inputs['pix_distribs'] (savp_model.py:252-255,408-410,647-653: designated-pixel distributions pushed through the predicted
     transformations, a visual-servoing output no training loss reads) is not on the MI355X path: a batch that carries it is refused
@@ -1468,10 +1512,13 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         self.lpips_weights = kwargs.pop('lpips_weights', None)
         # opt-in of the designated-pixel distribution outputs (pix_distribs=True, or SAVP_PIX_DISTRIBS=1); without it the key is refused
         self.pix_distribs = pix_distribs_opt_in(kwargs.pop('pix_distribs', None))
+        # skip Adam updates on non-finite gradients and report gradient norms (guard=True, or SAVP_GUARD=1); ignored by a mode='test' model
+        guard = kwargs.pop('guard', None)
         super(SAVPVideoPredictionModel, self).__init__(generator_fn, discriminator_fn, *args, **kwargs)
         if self.mode != 'train':
             self.discriminator_fn = None
         self.deterministic = not self.hparams.nz
+        self.guard = guard_enabled(guard, self.mode)
         self.engine = None
         self._shares = None                    # build_graph(share_with=...): the model whose variables this one reads
 
@@ -1508,7 +1555,8 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         images = inputs['images']
         B = images.shape[0]
         self.engine = SAVPEngine(self.hparams, tuple(images.shape[2:]), B, mode=self.mode, values=values, seed=seed,
-                                 device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights, pix_distribs=P, store=store)
+                                 device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights, pix_distribs=P, store=store,
+                                 guard=self.guard)
         self.saveable_variables = self.engine.store.names()
         self.post_init_ops = []
         self.outputs = {}
@@ -1616,6 +1664,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
                 out[k] = l
             out['d_loss'], out['g_loss'] = info['d_loss'], info['g_loss']        # d_loss is 0 without a discriminator (the reference omits it then)
             out['loss'] = info['d_loss'] + info['g_loss']
+            out.update(self.health_scalars(info))
         self._stage(inputs)
         noise = eng.default_noise()
         gen = eng.generate(noise)
@@ -1624,6 +1673,18 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         out['ground_truth_sampling_mean'] = gt[:, eng.B if eng.nz else 0:].float().mean()
         if eng.nz:
             out['ground_truth_sampling_mean_enc'] = gt[:, :eng.B].float().mean()
+        return out
+
+    @staticmethod
+    def health_scalars(info):
+        """The guard's scalar summaries of a train step's `info`: grad_norm_d/g and skipped_steps_d/g (device scalars); empty for a step
+        without the guard (and for the forward-only losses of a validation batch)."""
+        out = OrderedDict()
+        health = (info or {}).get('health') or {}
+        for grp in ('d', 'g'):
+            if 'grad_norm_' + grp in health:
+                out['grad_norm_' + grp] = health['grad_norm_' + grp]
+                out['skipped_steps_' + grp] = health['skipped_' + grp]
         return out
 
     def image_summary_fn(self, inputs=None, noise=None):
