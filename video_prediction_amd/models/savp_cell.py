@@ -12,6 +12,9 @@ MI355X-first layout decisions:
     images]) are never materialised by copies: producers write straight into channel slices of the consumer's
     concat buffer, gradients are read back from the same slices;
   * the posterior and prior unrolls share weights, so they run as ONE unroll of batch 2B (all ops are per-sample).
+
+What a recurrent ladder layer runs (ConvLSTM / ConvGRU with or without their norms, ablation_rnn's convolution) is one class per variant in
+conv_rnn_cells.py; this module builds the chosen class per layer (L['cell']) and calls only its interface.
 """
 import os
 
@@ -19,7 +22,7 @@ import torch
 
 from .. import kernels as K
 from .. import lib
-from ..engine import ConcatConv, ConvLayer, same_pad_before, copy_view, add_views, prep_layers
+from ..engine import ConcatConv, ConvLayer, same_pad_before, copy_view, prep_layers
 from ..variables import ACTIVATIONS, NORM_SCOPES, down_scope, layer_specs, num_masks, up_scope
 
 CONV_STATS = os.environ.get('SAVP_CONV_STATS', '1') == '1'      # developer A/B switch of the conv-epilogue statistics
@@ -183,6 +186,9 @@ def check_kernel_size(hp):
         raise NotImplementedError('kernel_size = %r: the transformation kernels take at most 49 taps' % (tuple(hp.kernel_size),))
 
 
+from . import conv_rnn_cells      # noqa: E402  (the cells build on Act, Norm and norm_fwd / norm_bwd above: the two modules import each other)
+
+
 class SAVPGenerator(object):
     def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0), pix=0):
         """cond = (n_actions, n_states): widths of inputs['actions'] / inputs['states'] (savp_model.py:411-444): [actions_t | state_t]
@@ -201,17 +207,6 @@ class SAVPGenerator(object):
         # norm_layer = 'layer': every norm_layer site (the ladder's layers, ablation_rnn's conv_h<i>, the 3x3 heads) is a layer norm,
         # variables under <scope>/LayerNorm/ (csrc/group_norm.hip with one group; the heads' merged launch: one group per head)
         self.ln = hp.norm_layer == 'layer'
-        # conv_rnn_norm_layer = 'layer' inside the ConvLSTM cell (separate_norms, rnn_ops.py:147-165): the gate convolution (no bias),
-        # a layer norm per gate (one G = 4 launch), the pointwise state update, a layer norm of the new state, h' (csrc/ln_lstm.hip)
-        self.cell_ln = bool(hp.conv_rnn_norm_layer == 'layer' and not hp.ablation_conv_rnn_norm)
-        # The conv-RNN cell WITHOUT a normaliser (ConvLSTM, rnn_ops.py:122-125: the gate convolution then has a bias; :148-165 with
-        # normalizer_fn None.  ConvGRU, :220-223: both convolutions have one, gates/bias and candidate/bias; :246-263 with normalizer_fn None):
-        # conv_rnn_norm_layer = 'none', or ablation_conv_rnn_norm (savp_model.py:380-384: the cell is built without one and the layer's OUTPUT
-        # h -- not the state handed to the next step -- goes through normalizer_fn, variables under <cell scope>/InstanceNorm/).
-        self.cell_plain = bool(hp.conv_rnn_norm_layer == 'none' or hp.ablation_conv_rnn_norm)
-        self.out_norm = bool(hp.ablation_conv_rnn_norm)
-        if self.out_norm and hp.conv_rnn_norm_layer == 'none':
-            raise TypeError("ablation_conv_rnn_norm with conv_rnn_norm_layer='none': the reference calls normalizer_fn = None (savp_model.py:384)")
         # downsample_layer / upsample_layer / activation_layer (ops.py:1052-1098; savp_model.py:395-397).  conv2d: the strided SAME
         # convolution, ConvLayer kind 'down'; deconv2d: conv2d_transpose, kind 'deconv'; the _v2 names are aliases (variables.DOWN_SCOPES).
         # elu: the activation code of every norm_layer site of the cell (the ladder, ablation_rnn's conv_h<i>, the 3x3 heads).
@@ -265,11 +260,8 @@ class SAVPGenerator(object):
         # z, the `dense/kernel` / `weights` variables and z itself get zero gradients.  The layers therefore run without z channels and
         # those variables keep their (zero-initialised) gradients; pinned against the oracle, which computes the sums literally.
         tile = bool(hp.use_tile_concat)
-        if hp.conv_rnn == 'gru' and self.cell_plain and not self.abl_rnn and not tile and hp.where_add == 'all' and zw:
-            # no norm stands behind the bare cell's two convolutions, so dense(z) (gates/weights, candidate/weights) is NOT cancelled there
-            raise NotImplementedError("conv_rnn='gru' without a cell normaliser (conv_rnn_norm_layer='none' or ablation_conv_rnn_norm) with "
-                                      "use_tile_concat=False, where_add='all' and a latent: the untiled latent of the bare cell is not on "
-                                      "the HIP path")
+        # which conv-RNN cell the recurrent layers run (the matrix of DESIGN.md section 1), and whether its output takes a norm of its own
+        cell, out_norm = conv_rnn_cells.cell_class(hp, zw)
         zr = zw if (hp.where_add == 'all' and tile) else 0              # tiled channels in a conv-RNN's input [x | actions state z | h]
         g = train
         # bf16 storage of tensors whose ONLY readers are convolutions of the bf16 datapath (round 4; the cell input [x | z | h] and the
@@ -327,92 +319,8 @@ class SAVPGenerator(object):
             pre16 = f % 8 == 0 and (i < self.ne or L['in'].v.dtype == torch.bfloat16 or not self.act16)
             L['pre'] = Act((T1, N, h_, w_, f), dev, grad=g, grad_dtype=a16 if pre16 else torch.float32)
             L['norm'] = self._norm(s, f, bias=L['conv'].bias_name)
-            if use_rnn and self.abl_rnn:
-                r = prefix + 'conv_h%d/' % i
-                L['a'] = Act((T1, N, h_, w_, ceil4(f + zr)), dev, grad=g, dtype=a16 if ceil4(f + zr) % 8 == 0 else torch.float32)
-                L['pre2'] = Act((T1, N, h_, w_, f), dev, grad=g, grad_dtype=a16 if f % 8 == 0 else torch.float32)
-                L['rconv'] = ConvLayer(store, r + 'conv2d/kernel', r + 'conv2d/bias', 'conv', (5, 5), (1, 1), (2, 2), cx_pad=ceil4(f + zr))
-                L['n2'] = self._norm(r, f, bias=r + 'conv2d/bias')
-            elif use_rnn and hp.conv_rnn == 'gru':
-                # Conv2DGRUCell (rnn_ops.py:174-267): a = [x | z | h_prev | r*h_prev]; the gates conv reads the first
-                # f+zc+f channels of the same buffer (a channel-slice view), the candidate conv reads all of it
-                r = prefix + 'gru_h%d/conv2dgru_cell/' % i
-                L['cin1'] = f + zr + f
-                L['a'] = Act((T1, N, h_, w_, f + zr + 2 * f), dev, grad=g)
-                L['gates'] = Act((T1, N, h_, w_, 2 * f), dev, grad=g)
-                L['cand'] = Act((T1, N, h_, w_, f), dev, grad=g)
-                L['u'] = torch.empty(T1, N, h_, w_, f, device=dev)
-                L['du'] = torch.empty(N, h_, w_, f, device=dev) if g else None
-                L['dh_tmp'] = torch.empty(N, h_, w_, f, device=dev) if g else None
-                # without a normaliser the two convolutions carry a bias (rnn_ops.py:220-223) and the gate blocks are pointwise
-                L['rconv'] = ConvLayer(store, r + 'gates/kernel', (r + 'gates/bias') if self.cell_plain else None, 'conv', (5, 5), (1, 1), (2, 2))
-                L['cconv'] = ConvLayer(store, r + 'candidate/kernel', (r + 'candidate/bias') if self.cell_plain else None, 'conv', (5, 5),
-                                       (1, 1), (2, 2))
-                if not self.cell_plain:
-                    L['n1'] = Norm(store, r + 'gates/reset_update/', T1, N, 2 * f, dev)
-                    L['n2'] = Norm(store, r + 'candidate/state/', T1, N, f, dev)
-                    # a plane the one-workgroup gate blocks cannot hold (gru_large_layers): the chunked two-pass blocks and their workspace;
-                    # 'gru_large_calls' counts the launches of those blocks (tests read it)
-                    L['gru_large'] = h_ * w_ > K.GRU_SMALL_MAX_HW
-                    if L['gru_large'] and train:
-                        # Training at such frames is not pinned against the oracle yet: the ConvLSTM twin's train step misses the fp64 gradient
-                        # bounds at 64x80 (a video discriminator kernel) and at 96x96 (the latent LSTM's kernel), see profiles/gru_large.md.
-                        # The backward blocks below are wired and tested on their own; this refusal goes when that finding is settled.
-                        raise NotImplementedError("conv_rnn='gru' with its instance norm on a conv-RNN plane of %dx%d = %d pixels (layer h%d, above "
-                                                  "%d): mode='train' is not offered at this frame size yet, generation and evaluation are "
-                                                  "(profiles/gru_large.md)" % (h_, w_, h_ * w_, i, K.GRU_SMALL_MAX_HW))
-                    if L['gru_large']:
-                        L['gru_ws'] = K.convgru_large_ws(dev, N, h_ * w_, f)
-                        L['gru_large_calls'] = 0
-                if self.out_norm:          # ablation_conv_rnn_norm: normalizer_fn(h) on the layer's output, the state stays un-normalised
-                    L['h_raw'] = Act((T1, N, h_, w_, f), dev, grad=g)
-                    L['onorm'] = self._norm(prefix + 'gru_h%d/' % i, f, hp.conv_rnn_norm_layer)
-            elif use_rnn:
-                r = prefix + 'lstm_h%d/basic_conv2dlstm_cell/' % i
-                # fused ConvLSTM cell of the bf16 datapath: the gate convolution's epilogue produces the statistics of the first
-                # instance norm and stores the gate pre-activations as bf16 (csrc/conv_ring.hip) -> conv + 2 launches per cell
-                L['fused'] = (K.PRECISION['value'] == 1 and os.environ.get('SAVP_FUSED_CELL', '1') == '1' and not self.cell_plain and
-                              not self.cell_ln and
-                              h_ % 8 == 0 and w_ % 8 == 0 and 16 <= f <= 256 and (f & (f - 1)) == 0 and (f + zr + f) % 8 == 0)
-                # The cell's input buffer [x | z | h] and the gate gradient are held in bf16 (round 3: validated on MI355X, identical
-                # numbers -- their only readers are the gate convolution's FPROP / DGRAD / WGRAD, which round to bf16 when they stage
-                # their operands anyway -- and half the bytes; step time unchanged within noise, 61.04 vs 61.21 ms).  The producers
-                # (instance norm of the layer's conv, tile_channels, the h' output and the gate gradient of the gate kernels) write bf16
-                # through their out_bf16 / h_bf16 / dgates_bf16 flags.  SAVP_BF16_ACT=0 / SAVP_BF16_DGATES=0 keep fp32 tensors.
-                a_dt = torch.bfloat16 if (L['fused'] and os.environ.get('SAVP_BF16_ACT', '1') == '1') else torch.float32
-                L['a'] = Act((T1, N, h_, w_, f + zr + f), dev, grad=g, dtype=a_dt)
-                dg_dt = torch.bfloat16 if (L['fused'] and g and os.environ.get('SAVP_BF16_DGATES', '1') == '1') else torch.float32
-                L['gates'] = Act((T1, N, h_, w_, 4 * f), dev, grad=g, dtype=torch.bfloat16 if L['fused'] else torch.float32,
-                                 grad_dtype=dg_dt)
-                L['dg_raw'] = torch.empty(N, h_, w_, 4 * f, device=dev) if dg_dt == torch.bfloat16 else None
-                L['c'] = Act((T1, N, h_, w_, f), dev, grad=False)
-                L['dc'] = [torch.empty(N, h_, w_, f, device=dev), torch.empty(N, h_, w_, f, device=dev)] if g else None
-                L['rconv'] = ConvLayer(store, r + 'kernel', (r + 'bias') if self.cell_plain else None, 'conv', (5, 5), (1, 1), (2, 2))
-                if not self.cell_plain and not self.cell_ln:
-                    # the gate convolution's own kernel (bf16 datapath, csrc/conv_gate.hip); where a tile holds whole images (planes of <= 256
-                    # pixels) also the interleaved pack: savp_convlstm_cell_fwd then runs the whole cell forward as one launch
-                    L['rconv'].enable_gate_pack(cell=bool(L['fused']) and h_ * w_ <= 256)
-                if self.cell_ln:
-                    # input / transform / forget / output: one G = 4 launch over the gate tensor, parameters gathered per step
-                    L['gn4'] = ConcatNorm([Norm(store, r + nm + '/', T1, N, f, dev, groups=1) for nm in ('input', 'transform', 'forget', 'output')],
-                                          T1, N, dev)
-                    L['nS'] = Norm(store, r + 'state/', T1, N, f, dev, groups=1)
-                    L['gnv'] = Act((T1, N, h_, w_, 4 * f), dev, grad=g)          # the normalised gates and their gradient
-                    L['cpre'] = Act((T1, N, h_, w_, f), dev, grad=g)             # the state before its norm
-                    L['dcn'] = torch.empty(N, h_, w_, f, device=dev) if g else None
-                elif not self.cell_plain:
-                    L['n1'] = Norm(store, r + 'input_transform_forget_output/', T1, N, 4 * f, dev)
-                    L['n2'] = Norm(store, r + 'state/', T1, N, f, dev)
-                if self.out_norm:
-                    L['h_raw'] = Act((T1, N, h_, w_, f), dev, grad=g)
-                    L['onorm'] = self._norm(prefix + 'lstm_h%d/' % i, f, hp.conv_rnn_norm_layer)
-                # The data gradient of the gate convolution leaves the tiled-z channels of [x | z | h] out (their gradient is a per-sample
-                # sum, taken once over all timesteps from region sums of the gate gradient: csrc/tiled_z.hip), which keeps its column count
-                # on a tile boundary (72 / 136 / 264 -> 64 / 128 / 256; KTH's nz = 32: 96 / 160 / 288 -> 64 / 128 / 256).  bf16 datapath (the ring kernel owns the column gap).
-                L['zless'] = bool(g and zr and not cw and L['fused'] and os.environ.get('SAVP_ZLESS_DGRAD', '1') == '1' and
-                                  K.tiled_z_ok(h_, w_, 4 * f, zr, L['rconv'].geom))
-                if L['zless']:
-                    L['weff'] = torch.empty(25, 4 * f, K.tiled_z_pad(zr), device=dev)
+            if use_rnn:
+                L['cell'] = cell(self, L, prefix, out_norm)          # its buffers, ConvLayers and Norms go into L (conv_rnn_cells.py)
             else:
                 L['out'] = None
             self.layers.append(L)
@@ -551,7 +459,6 @@ class SAVPGenerator(object):
                 self.dzW, self.dzb = store.grad64(z + 'kernel'), store.grad64(z + 'bias')      # float64 accumulators (one workgroup per sample adds to them)
                 self.z_gates = torch.empty(T1, N, 4 * nz, device=dev)
                 self.z_cs = torch.empty(T1, N, nz, device=dev)
-        self.gru = hp.conv_rnn == 'gru'
         # ---- learn_initial_state (savp_model.py:295-307,344-352): the conv-RNN states and the rnn_z state start from variables
         # `generator/initial_state_<i>/initial_state` (i = position in nest.flatten of {'conv_rnn_states': [...], 'rnn_z_state': ...}: layer
         # order, LSTM tuples as (c, h), the latent cell last), tiled over the batch; both unrolls (N = 2B) share them.  Forward: a broadcast
@@ -567,13 +474,8 @@ class SAVPGenerator(object):
                 assert tuple(store[name].shape) == tuple(shape), (name, tuple(store[name].shape), shape)
                 return store[name], ((store.grad64(name) if acc64 else store.grad(name)) if g else None)
             for L in self.layers:
-                if not L['rnn']:
-                    continue
-                hw_f = L['hw'] + (L['f'],)
-                if not self.gru:
-                    L['c0v'], L['c0g'] = var(hw_f)
-                    L['c0'] = torch.empty((N,) + hw_f, device=dev)
-                L['h0v'], L['h0g'] = var(hw_f)
+                if L['rnn']:
+                    L['cell'].make_initial_state(var)
             if self.use_rnn_z and hp.rnn == 'gru':               # GRUCell: the state is h alone (savp_model.py:288-291)
                 self.z_h0, self.z_dh0 = var((nz,), acc64=True)
             elif self.use_rnn_z:
@@ -597,8 +499,10 @@ class SAVPGenerator(object):
             self.heads_pre = Act((T1, N, H, W, self.nheads * ngf), dev, grad=g,
                                  grad_dtype=a16 if (self.nheads * ngf) % 8 == 0 else torch.float32)
             head_convs = [self.heads_conv]
-        self.convs = [L['conv'] for L in self.layers] + [L['rconv'] for L in self.layers if L['rnn']] + \
-                     [L['cconv'] for L in self.layers if L['rnn'] and self.gru and not self.abl_rnn] + \
+        # (the cells' convolutions kind by kind -- every layer's gate convolution, then every GRU candidate convolution: prep_layers packs
+        #  the weights and finish_weight_grad folds the gradients in this order)
+        cell_convs = [L['cell'].convs() for L in self.layers if L['rnn']]
+        self.convs = [L['conv'] for L in self.layers] + [c for kind in zip(*cell_convs) for c in kind] + \
                      ([self.fc_z] if (self.use_rnn_z and self.abl_rnn) else []) + \
                      tf_convs + head_convs + ([self.scratch_out] if self.scratch else []) + [self.masks_out]
         # ---- pix_distribs: one launch after the unroll (pix_distribs_forward); the slots in the reference's order (:598-621) ----
@@ -642,8 +546,8 @@ class SAVPGenerator(object):
         if self.merge_heads:
             self.heads_norm.prep()
         for L in self.layers:
-            if 'gn4' in L:
-                L['gn4'].prep()
+            if L['rnn']:
+                L['cell'].prep()
 
     # ---------------------------------------------------------------------------------------------------------
     def _out_views(self, L, t):
@@ -701,10 +605,7 @@ class SAVPGenerator(object):
         if self.learn_init:                # step 0's state slots <- the learned initial states, tiled over the batch
             for L in self.layers:
                 if L['rnn']:
-                    f, hoff = L['f'], L['f'] + L['zr']
-                    L['a'].v[0][..., hoff:hoff + f].copy_(L['h0v'])
-                    if not self.gru:
-                        L['c0'].copy_(L['c0v'])
+                    L['cell'].load_initial_state()
         in0, maskin = self.layers[0]['in'], self.maskin
         # the first frame feeds every step (savp_model.py:399-400): ONE launch writes it into all T1 steps' buffers -- time is the
         # kernel's sample index (source stride 0), the N*H*W pixels of a step its pixel index
@@ -747,104 +648,10 @@ class SAVPGenerator(object):
                 if ck not in L:
                     L[ck] = (CONV_STATS and f <= 256 and (f & (f - 1)) == 0 and L['conv'].stats_ok(L['in'].v[t], L['pre'].v[t]))
                 st = K.stats_ws(self.dev, N, f) if L[ck] else None
-                nrm = L['norm']
-                if L['rnn'] and self.abl_rnn:
-                    a = L['a']
-                    self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, [a.v[t][..., 0:f]], t)
-                    self._conv_norm(('abl', L['idx']), L['rconv'], a.v[t], L['pre2'].v[t], L['n2'], self._out_views(L, t), t)
-                elif L['rnn'] and self.gru:
-                    L['conv'].forward(L['in'].v[t], L['pre'].v[t], stats=st)
-                    a = L['a']
-                    hs, rs_, cin1 = f + L['zr'], f + L['zr'] + f, L['cin1']
-                    norm_fwd(nrm, L['pre'].v[t], [a.v[t][..., 0:f]], nrm.mean[t], nrm.rstd[t],
-                             act=self.act, eps=EPS_IN, stats=st, stats_shift=L['conv'].bias if st is not None else None)
-                    hprev = a.v[t][..., hs:hs + f]
-                    nxt_h = [a.v[t + 1][..., hs:hs + f]] if t + 1 < T1 else []
-                    if self.cell_plain:
-                        L['rconv'].forward(a.v[t][..., 0:cin1], L['gates'].v[t])              # conv + bias
-                        K.convgru_plain_gates_fwd(L['gates'].v[t], hprev, L['u'][t], a.v[t][..., rs_:rs_ + f])
-                        L['cconv'].forward(a.v[t], L['cand'].v[t])                            # conv + bias
-                        hdst = ([L['h_raw'].v[t]] if self.out_norm else self._out_views(L, t)) + nxt_h
-                        K.convgru_plain_out_fwd(L['cand'].v[t], hprev, L['u'][t], hdst)
-                        if self.out_norm:
-                            on = L['onorm']
-                            norm_fwd(on, L['h_raw'].v[t], self._out_views(L, t), on.mean[t], on.rstd[t], act='none', eps=EPS_IN)
-                        continue
-                    n1, n2 = L['n1'], L['n2']
-                    L['rconv'].forward(a.v[t][..., 0:cin1], L['gates'].v[t], use_bias=False)
-                    if L['gru_large']:
-                        K.convgru_large_gates_fwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['u'][t],
-                                                  a.v[t][..., rs_:rs_ + f], L['gru_ws'], eps=EPS_IN)
-                        L['cconv'].forward(a.v[t], L['cand'].v[t], use_bias=False)
-                        K.convgru_large_out_fwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t],
-                                                self._out_views(L, t) + nxt_h, L['gru_ws'], eps=EPS_IN)
-                        L['gru_large_calls'] += 2
-                        continue
-                    K.convgru_gates_fwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['u'][t],
-                                        a.v[t][..., rs_:rs_ + f], eps=EPS_IN)
-                    L['cconv'].forward(a.v[t], L['cand'].v[t], use_bias=False)
-                    K.convgru_out_fwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t],
-                                      self._out_views(L, t) + nxt_h, eps=EPS_IN)
-                elif L['rnn'] and self.cell_plain:
-                    a = L['a']
-                    self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, [a.v[t][..., 0:f]], t)
-                    L['rconv'].forward(a.v[t], L['gates'].v[t])                       # conv + bias
-                    nxt_h = [a.v[t + 1][..., f + L['zr']:f + L['zr'] + f]] if t + 1 < T1 else []
-                    hdst = ([L['h_raw'].v[t]] if self.out_norm else self._out_views(L, t)) + nxt_h
-                    K.convlstm_gates_fwd(L['gates'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), None, None, None, None, L['c'].v[t], hdst, None)
-                    if self.out_norm:
-                        on = L['onorm']
-                        norm_fwd(on, L['h_raw'].v[t], self._out_views(L, t), on.mean[t], on.rstd[t], act='none', eps=EPS_IN)
-                elif L['rnn'] and self.cell_ln:
-                    a, g4, nS = L['a'], L['gn4'], L['nS']
-                    self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, [a.v[t][..., 0:f]], t)
-                    L['rconv'].forward(a.v[t], L['gates'].v[t], use_bias=False)
-                    K.groupnorm_act_fwd(L['gates'].v[t], g4.gamma, g4.beta, [L['gnv'].v[t]], g4.mean[t], g4.rstd[t], groups=4, act='none')
-                    K.lnlstm_state_fwd(L['gnv'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), L['cpre'].v[t])
-                    K.groupnorm_act_fwd(L['cpre'].v[t], nS.gamma, nS.beta, [L['c'].v[t]], nS.mean[t], nS.rstd[t], groups=1, act='none')
-                    outs = self._out_views(L, t)
-                    if t + 1 < T1:
-                        outs.append(a.v[t + 1][..., f + L['zr']:f + L['zr'] + f])
-                    K.lnlstm_out_fwd(L['gnv'].v[t], L['c'].v[t], outs)
-                elif L['rnn']:
-                    a = L['a']
-                    self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, [a.v[t][..., 0:f]], t)
-                    stats1 = s1 = None
-                    if L['fused']:
-                        stats1, s1 = K.lstm_stats_ws(self.dev, N, f)
-                    cp = L.get('cell_prof')                  # bench.py: HIP events around the whole cell (gate conv + gate passes)
-                    if cp is not None:
-                        ce0, ce1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        ce0.record()
-                    outs = self._out_views(L, t)
-                    if t + 1 < T1:
-                        outs.append(a.v[t + 1][..., f + L['zr']:f + L['zr'] + f])
-                    n1, n2 = L['n1'], L['n2']
-                    gk = L.get('gate_ktimer')                # bench.py: the gate-block launch's own begin / end stamps
-                    gargs = (L['gates'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), n1.gamma, n1.beta, n2.gamma, n2.beta, L['c'].v[t], outs,
-                             [n1.mean[t], n1.rstd[t], n2.mean[t], n2.rstd[t]])
-                    # the whole cell as ONE host call (savp_convlstm_cell_fwd) unless a measurement wants the two launches apart
-                    ca = (L['rconv'].forward(a.v[t], L['gates'].v[t], use_bias=False, stats=s1, defer=True)
-                          if (FUSED_ENTRIES and cp is None and gk is None and K.fused_ok()) else None)
-                    if ca is not None:
-                        ck = L.get('cell_ktimer')            # bench.py: the one-launch cell's own begin / end stamps (the kernel takes the armed pair)
-                        if ck is not None:
-                            ck.arm()
-                        K.convlstm_cell_fwd(ca, K.convlstm_gates_fwd(*gargs, eps=EPS_IN, ws=self._lstm_ws(L), stats1=stats1, defer=True))
-                        if ck is not None:
-                            ck.taken()
-                    else:
-                        L['rconv'].forward(a.v[t], L['gates'].v[t], use_bias=False, stats=s1)
-                        if gk is not None:
-                            gk.arm()
-                        K.convlstm_gates_fwd(*gargs, eps=EPS_IN, ws=self._lstm_ws(L), stats1=stats1)
-                        if gk is not None:
-                            gk.taken()
-                    if cp is not None:
-                        ce1.record()
-                        cp.append((ce0, ce1))
+                if L['rnn']:
+                    L['cell'].forward(t, st)
                 else:
-                    self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, nrm, self._out_views(L, t), t)
+                    self._conv_in_act(L['conv'], L['in'].v[t], L['pre'].v[t], st, L['norm'], self._out_views(L, t), t)
             tslot = maskin.v[t][..., self.o_cdna:self.o_cdna + self.nk * C]
             ngf = self.hp.ngf
             if self.merge_heads:
@@ -970,15 +777,6 @@ class SAVPGenerator(object):
             norm_bwd(nrm, *nargs[:1], *nargs[3:], act=self.act, eps=EPS_IN, stats=st)
             L['conv'].backward_data(L['pre'].g[t], L['in'].g[t], beta=0)
 
-    def _lstm_ws(self, L):
-        """Scratch of the coalesced ConvLSTM gate kernels (one buffer shared by all layers: the launches are serial)."""
-        h, w = L['hw']
-        need = K.lstm_ws_floats(self.N, h * w, L['f'])
-        ws = getattr(self, '_lstm_ws_buf', None)
-        if ws is None or ws.numel() < need:
-            ws = self._lstm_ws_buf = torch.empty(max(need, K.lstm_ws_floats(self.N, self.H * self.W // 4, 32)), device=L["gates"].v.device)
-        return ws
-
     def backward(self, state_grad=False):
         """BPTT.  Expects self.gen.g (zero-initialised each step by the caller) to hold dL/dgen_images (and, with state_grad,
         self.gen_states.g to hold dL/dgen_states).
@@ -1067,110 +865,13 @@ class SAVPGenerator(object):
                 nb_last = None
             # decoder / encoder ladder in reverse
             for L in reversed(self.layers):
-                f = L['f']
                 dys = self._out_grads(L, t)
-                nrm = L['norm']
-                if L['rnn'] and self.abl_rnn:
-                    a, n2 = L['a'], L['n2']
-                    norm_bwd(n2, L['pre2'].v[t], self._out_views(L, t)[0], n2.mean[t], n2.rstd[t], dys, L['pre2'].g[t],
-                                       n2.dgamma, n2.dbeta, act=self.act, eps=EPS_IN)
-                    L['rconv'].backward_data(L['pre2'].g[t], a.g[t], beta=0)
-                    self._in_act_conv_bwd(L, t, a.v[t][..., 0:f], [a.g[t][..., 0:f]], None)
-                    continue
-                if L['rnn'] and self.gru:
-                    a = L['a']
-                    hs, rs_, cin1 = f + L['zr'], f + L['zr'] + f, L['cin1']
-                    if self.out_norm:
-                        on = L['onorm']
-                        norm_bwd(on, L['h_raw'].v[t], self._out_views(L, t)[0], on.mean[t], on.rstd[t], dys,
-                                 L['h_raw'].g[t], on.dgamma, on.dbeta, act='none', eps=EPS_IN)
-                        dys = [L['h_raw'].g[t]]
-                    if t + 1 < T1:
-                        dys.append(a.g[t + 1][..., hs:hs + f])
-                    hprev = a.v[t][..., hs:hs + f]
-                    if self.cell_plain:
-                        K.convgru_plain_out_bwd(L['cand'].v[t], hprev, L['u'][t], dys, L['cand'].g[t], L['du'], L['dh_tmp'])
-                    else:
-                        n1, n2 = L['n1'], L['n2']
-                        if L['gru_large']:
-                            K.convgru_large_out_bwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], dys,
-                                                    L['cand'].g[t], L['du'], L['dh_tmp'], n2.dgamma, n2.dbeta, L['gru_ws'], eps=EPS_IN)
-                        else:
-                            K.convgru_out_bwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], dys,
-                                              L['cand'].g[t], L['du'], L['dh_tmp'], n2.dgamma, n2.dbeta, eps=EPS_IN)
-                    L['cconv'].backward_data(L['cand'].g[t], a.g[t], beta=0)
-                    add_views([L['dh_tmp']], a.g[t][..., hs:hs + f])
-                    if self.cell_plain:
-                        K.convgru_plain_gates_bwd(L['gates'].v[t], hprev, L['du'], a.g[t][..., rs_:rs_ + f], L['gates'].g[t],
-                                                  a.g[t][..., hs:hs + f])
-                    elif L['gru_large']:
-                        K.convgru_large_gates_bwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'],
-                                                  a.g[t][..., rs_:rs_ + f], L['gates'].g[t], a.g[t][..., hs:hs + f], n1.dgamma, n1.dbeta,
-                                                  L['gru_ws'], eps=EPS_IN)
-                        L['gru_large_calls'] += 2
-                    else:
-                        K.convgru_gates_bwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'],
-                                            a.g[t][..., rs_:rs_ + f], L['gates'].g[t], a.g[t][..., hs:hs + f], n1.dgamma, n1.dbeta,
-                                            eps=EPS_IN)
-                    L['rconv'].backward_data(L['gates'].g[t], a.g[t][..., 0:cin1], beta=1)
-                    norm_bwd(nrm, L['pre'].v[t], a.v[t][..., 0:f], nrm.mean[t], nrm.rstd[t],
-                                       [a.g[t][..., 0:f]], L['pre'].g[t], nrm.dgamma, nrm.dbeta, act=self.act, eps=EPS_IN)
-                elif L['rnn'] and self.cell_plain:
-                    a = L['a']
-                    if self.out_norm:
-                        on = L['onorm']
-                        norm_bwd(on, L['h_raw'].v[t], self._out_views(L, t)[0], on.mean[t], on.rstd[t], dys,
-                                           L['h_raw'].g[t], on.dgamma, on.dbeta, act='none', eps=EPS_IN)
-                        dys = [L['h_raw'].g[t]]
-                    if t + 1 < T1:
-                        dys.append(a.g[t + 1][..., f + L['zr']:f + L['zr'] + f])
-                    dc_new = L['dc'][(t + 1) & 1] if t + 1 < T1 else None
-                    dc_prev = L['dc'][t & 1] if (t > 0 or self.learn_init) else None
-                    K.convlstm_gates_bwd(L['gates'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), None, None, None, None, None, dys, dc_new,
-                                         L['gates'].g[t], dc_prev, None)
-                    L['rconv'].backward_data(L['gates'].g[t], a.g[t], beta=0)
-                    self._in_act_conv_bwd(L, t, a.v[t][..., 0:f], [a.g[t][..., 0:f]], None)
-                    continue
-                elif L['rnn']:
-                    a = L['a']
-                    if t + 1 < T1:
-                        dys.append(a.g[t + 1][..., f + L['zr']:f + L['zr'] + f])
-                    dc_new = L['dc'][(t + 1) & 1] if t + 1 < T1 else None
-                    dc_prev = L['dc'][t & 1] if (t > 0 or self.learn_init) else None
-                    if self.cell_ln:
-                        g4, nS, gnv, cpre = L['gn4'], L['nS'], L['gnv'], L['cpre']
-                        c_prev = L['c'].v[t - 1] if t > 0 else L.get('c0')
-                        K.lnlstm_out_bwd(gnv.v[t], L['c'].v[t], dys, dc_new, L['dcn'], gnv.g[t])
-                        K.groupnorm_act_bwd(cpre.v[t], nS.gamma, nS.beta, nS.mean[t], nS.rstd[t], [L['dcn']], cpre.g[t], nS.dgamma, nS.dbeta,
-                                            groups=1, act='none')
-                        K.lnlstm_state_bwd(gnv.v[t], c_prev, cpre.g[t], gnv.g[t], dc_prev)
-                        K.groupnorm_act_bwd(L['gates'].v[t], g4.gamma, g4.beta, g4.mean[t], g4.rstd[t], [gnv.g[t]], L['gates'].g[t],
-                                            g4.dgamma, g4.dbeta, groups=4, act='none')
-                        L['rconv'].backward_data(L['gates'].g[t], a.g[t], beta=0)
-                        self._in_act_conv_bwd(L, t, a.v[t][..., 0:f], [a.g[t][..., 0:f]], None)
-                        continue
-                    n1, n2 = L['n1'], L['n2']
-                    bargs = (L['gates'].v[t], L['c'].v[t - 1] if t > 0 else L.get('c0'), n1.gamma, n1.beta, n2.gamma, n2.beta,
-                             [n1.mean[t], n1.rstd[t], n2.mean[t], n2.rstd[t]], dys, dc_new, L['gates'].g[t], dc_prev,
-                             [n1.dgamma, n1.dbeta, n2.dgamma, n2.dbeta])
-                    skip = (f, L['zr']) if L['zless'] else None
-                    nb = self._norm_bwd('nbstats', L, L['rconv'], L['gates'].g[t], a.g[t], nrm, L['pre'].v[t], skip)
-                    if nb is not None:
-                        nb['mean'], nb['rstd'] = nrm.mean[t], nrm.rstd[t]
-                    if FUSED_ENTRIES and K.fused_ok():       # gate block backward + the gate convolution's DGRAD: one host call
-                        K.convlstm_cell_bwd(L['rconv'].backward_data(L['gates'].g[t], a.g[t], beta=0, skip=skip, norm_bwd=nb, defer=True),
-                                            K.convlstm_gates_bwd(*bargs, eps=EPS_IN, ws=self._lstm_ws(L), dgates_raw=L.get('dg_raw'), defer=True))
-                    else:
-                        K.convlstm_gates_bwd(*bargs, eps=EPS_IN, ws=self._lstm_ws(L), dgates_raw=L.get('dg_raw'))
-                        L['rconv'].backward_data(L['gates'].g[t], a.g[t], beta=0, skip=skip, norm_bwd=nb)
-                    self._in_act_conv_bwd(L, t, a.v[t][..., 0:f], [a.g[t][..., 0:f]], nb['ws'] if nb is not None else None)
-                    continue
+                if L['rnn']:
+                    L['cell'].backward(t, dys)
                 else:
                     y0 = self._out_views(L, t)[0]
                     st_ = nb_last['ws'] if (L is self.layers[-1] and nb_last is not None and len(dys) == 1) else None
                     self._in_act_conv_bwd(L, t, y0, dys, st_)
-                    continue
-                L['conv'].backward_data(L['pre'].g[t], L['in'].g[t], beta=0)
             # d image -> previous step's generated frame where it was fed back (not ground truth)
             if t > 0:
                 K.select_bwd(self.gt_mask[t], [in0.g[t][..., 0:C], self.dimg_cdna if self.L == 1 else self.dimg_acc[t]] +
@@ -1178,26 +879,13 @@ class SAVPGenerator(object):
         if self.learn_init:                # gradients of the learned initial states: step 0's state gradients summed over the batch
             for L in self.layers:
                 if L['rnn']:
-                    f, hoff = L['f'], L['f'] + L['zr']
-                    L['h0g'].add_(L['a'].g[0][..., hoff:hoff + f].float().sum(0))
-                    if not self.gru:
-                        L['c0g'].add_(L['dc'][0].sum(0))
+                    L['cell'].initial_state_grad()
         # ---- weight gradients: one split-K GEMM per layer over all (t, n) ----------------------------------------
         for L in self.layers:
             b, pre = L['in'], L['pre']
             L['conv'].backward_weights(b.flat(b.v), pre.flat(pre.g), feeds_instance_norm=True)
-            if L['rnn'] and self.abl_rnn:
-                a, p2 = L['a'], L['pre2']
-                L['rconv'].backward_weights(a.flat(a.v), p2.flat(p2.g), feeds_instance_norm=True)
-            elif L['rnn'] and self.gru:
-                a, gt, cd = L['a'], L['gates'], L['cand']
-                L['rconv'].backward_weights(a.flat(a.v)[..., 0:L['cin1']], gt.flat(gt.g))
-                L['cconv'].backward_weights(a.flat(a.v), cd.flat(cd.g))
-            elif L['rnn']:
-                a, gt = L['a'], L['gates']
-                L['rconv'].backward_weights(a.flat(a.v), gt.flat(gt.g))
-                if 'gn4' in L:
-                    L['gn4'].finish()
+            if L['rnn']:
+                L['cell'].backward_weights()
         hl = self.h_last
         if self.tf == 'cdna':
             hs = self.hsmall
@@ -1231,14 +919,8 @@ class SAVPGenerator(object):
             b = L['in']
             if L['zc']:
                 K.colsum(b.flat(b.g)[..., L['zoff_in'] + cw:L['zoff_in'] + cw + nz], drz, per_row=True)
-            if L['rnn'] and L['zr'] and L.get('zless'):
-                # z gradient of the gate convolution from the gate gradients of all timesteps (the DGRADs left those channels out)
-                gt = L['gates']
-                K.tiled_z_weff(L['rconv'].W, L['rconv'].geom, L['f'], nz, L['weff'])
-                K.tiled_z_grad(gt.flat(gt.g), L['weff'], drz.reshape(T1 * N, nz), beta=1)
-            elif L['rnn'] and L['zr']:
-                a = L['a']
-                K.colsum(a.flat(a.g)[..., L['f'] + cw:L['f'] + cw + nz], drz, per_row=True)
+            if L['rnn'] and L['zr']:
+                L['cell'].z_gradient(drz)
         if self.use_rnn_z and self.abl_rnn:               # tanh(dense(z)) backward: d pre = d rnn_z * (1 - rnn_z^2)
             dpre = self.fcz_pre.g.reshape(T1, N, nz)
             torch.mul(self.rnn_z.v, self.rnn_z.v, out=dpre)
