@@ -717,6 +717,24 @@ int savp_convgru_large_gates_fwd(void* stream, const SavpGruLargeArgs* a);
 int savp_convgru_large_out_fwd(void* stream, const SavpGruLargeArgs* a);
 int savp_convgru_large_out_bwd(void* stream, const SavpGruLargeArgs* a);
 int savp_convgru_large_gates_bwd(void* stream, const SavpGruLargeArgs* a);
+/* ln_gru.hip: the four blocks with LAYER norms inside the cell (rnn_ops.py:234-267 with separate_norms = True, i.e. conv_rnn_norm_layer =
+ * 'layer'): r = sigmoid(LN(pre[..., :F])), u = sigmoid(LN(pre[..., F:])), c = tanh(LN(pre)) with LN = tf.contrib.layers.layer_norm --
+ * statistics per sample over (HW, F) of that tensor, biased variance, eps as given (1e-12).  Same fields of SavpGruLargeArgs, same
+ * overwrite / accumulate contract of dh, planes of ANY size HW >= 1, and the two-pass structure of gru_large.hip (per-chunk float64
+ * partials STORED to `ws`, folded in a fixed order; no fp32 atomics, nothing to clear, nothing allocated: legal in a captured graph).
+ * What differs:
+ *  gamma, beta : [2F] = (reset | update) for the gates stage, [F] for the output stage
+ *  mean, rstd  : [N][2] (reset, update) for the gates stage, [N][1] for the output stage; 4-byte aligned is enough
+ *  dgamma/dbeta: [2F] / [F] float64 accumulators, per CHANNEL as before
+ *  F <= 1024   : the apply pass holds 4 * F float64 totals in LDS
+ * savp_convgru_ln_chunk / savp_convgru_ln_ws_bytes: the pixels per workgroup and the bytes of `ws` ([N][chunks][4][F] float64).
+ * SAVP_EINVAL, without a launch: as for savp_convgru_large_*, and F > 1024. */
+int32_t savp_convgru_ln_chunk(int32_t N, int32_t HW);
+int64_t savp_convgru_ln_ws_bytes(int32_t N, int32_t HW, int32_t F);
+int savp_convgru_ln_gates_fwd(void* stream, const SavpGruLargeArgs* a);
+int savp_convgru_ln_out_fwd(void* stream, const SavpGruLargeArgs* a);
+int savp_convgru_ln_out_bwd(void* stream, const SavpGruLargeArgs* a);
+int savp_convgru_ln_gates_bwd(void* stream, const SavpGruLargeArgs* a);
 
 /* uint8 frames [B, T, frame] -> float32 time-major [T, B, frame] * (1/255): tf.image.convert_image_dtype (base_dataset.py:187)
  * + transpose_batch_time (tf_utils.py:118-122) for batches delivered by libsavp_io.so (include/savp_io.h); frame % 4 == 0 */

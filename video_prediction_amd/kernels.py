@@ -1799,6 +1799,61 @@ def convgru_large_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, 
     acc.finish()
 
 
+# the cell with LAYER norms inside (conv_rnn_norm_layer = 'layer', csrc/ln_gru.hip): the same two-pass blocks for a plane of any size;
+# gamma / beta are [2F] = (reset | update) or [F], mean / rstd are [N, 2] or [N, 1], dgamma / dbeta stay per channel
+LN_GRU_MAX_F = 1024               # LG_MAX_F
+
+
+def convgru_ln_chunk(N, HW):
+    """Pixels per workgroup of the convgru_ln_* launchers (savp_convgru_ln_chunk restated): the rule of convgru_large_chunk."""
+    return convgru_large_chunk(N, HW)
+
+
+def convgru_ln_ws_bytes(N, HW, F):
+    """Bytes of the float64 workspace [N, chunks, 4, F] one convgru_ln_* call needs (savp_convgru_ln_ws_bytes restated)."""
+    return convgru_large_ws_bytes(N, HW, F)
+
+
+def convgru_ln_ws(device, N, HW, F):
+    """A workspace for the convgru_ln_* calls of one layer: allocated once by the caller, its contents never matter between calls."""
+    return torch.empty(convgru_ln_ws_bytes(N, HW, F) // 8, dtype=torch.float64, device=device)
+
+
+def convgru_ln_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, ws, eps=EPS_LN):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
+    a.g.u, a.g.rh = _p(u), view(rh)
+    lib.check(_L().savp_convgru_ln_gates_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_gates_fwd')
+
+
+def convgru_ln_out_fwd(pre, h, gamma, beta, mean, rstd, u, outs, ws, eps=EPS_LN):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
+    a.g.u = _p(u)
+    a.g.nout = len(outs)
+    _set_views(a.g.out, outs)
+    lib.check(_L().savp_convgru_ln_out_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_out_fwd')
+
+
+def convgru_ln_out_bwd(pre, h, gamma, beta, mean, rstd, u, dys, dpre, du, dh, dgamma, dbeta, ws, eps=EPS_LN):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
+    a.g.u = _p(u)
+    a.g.ndy = len(dys)
+    _set_views(a.g.dy, dys)
+    a.g.dpre, a.g.du, a.g.dh = _p(dpre), _p(du), view(dh)
+    acc = _Acc64(dgamma, dbeta)
+    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
+    lib.check(_L().savp_convgru_ln_out_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_out_bwd')
+    acc.finish()
+
+
+def convgru_ln_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma, dbeta, ws, eps=EPS_LN):
+    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
+    a.g.du, a.g.drh, a.g.dpre, a.g.dh = _p(du), view(drh), _p(dpre), view(dh)
+    acc = _Acc64(dgamma, dbeta)
+    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
+    lib.check(_L().savp_convgru_ln_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_gates_bwd')
+    acc.finish()
+
+
 GAN_TYPES = {'LSGAN': 0, 'GAN': 1, 'SNGAN': 2}
 
 

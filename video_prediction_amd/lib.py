@@ -158,6 +158,8 @@ def _declare(lib):
     _sig(lib, 'savp_jpeg_workspace_bytes', [P(SavpJpegArgs)], restype=c_i64)
     _sig(lib, 'savp_convgru_large_chunk', [c_i32, c_i32])
     _sig(lib, 'savp_convgru_large_ws_bytes', [c_i32, c_i32, c_i32], restype=c_i64)
+    _sig(lib, 'savp_convgru_ln_chunk', [c_i32, c_i32])
+    _sig(lib, 'savp_convgru_ln_ws_bytes', [c_i32, c_i32, c_i32], restype=c_i64)
     _sig(lib, 'savp_arena_health_chunk', [])
     _sig(lib, 'savp_arena_health_ws_bytes', [c_i64], restype=c_i64)
     for name, argtypes in _EXTRA_SIGS.items():
@@ -492,6 +494,9 @@ class SavpGruLargeArgs(ctypes.Structure):
 
 
 for _n in ('savp_convgru_large_gates_fwd', 'savp_convgru_large_out_fwd', 'savp_convgru_large_out_bwd', 'savp_convgru_large_gates_bwd'):
+    register(_n, [c_vp, ctypes.POINTER(SavpGruLargeArgs)])
+# the layer-norm cell's blocks (csrc/ln_gru.hip) take the same structure: mean / rstd are [N][G] there
+for _n in ('savp_convgru_ln_gates_fwd', 'savp_convgru_ln_out_fwd', 'savp_convgru_ln_out_bwd', 'savp_convgru_ln_gates_bwd'):
     register(_n, [c_vp, ctypes.POINTER(SavpGruLargeArgs)])
 register('savp_gan_loss', [c_vp, c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_i32])
 register('savp_fold_f64', [c_vp, c_vp, c_i64, c_vp, c_vp])

@@ -19,10 +19,11 @@ from . import savp_cell as S      # Act, Norm, ConcatNorm, norm_fwd / norm_bwd a
                                   # so everything of S is read when a cell is built or called, never while this module is imported
 
 
-def cell_class(hp, zw=0):
+def cell_class(hp, zw=0, ln_gru=None):
     """(class, out_norm) of the conv-RNN layers under `hp`.  out_norm: ablation_conv_rnn_norm, the bare cell's output h -- not the state
-    handed to the next step -- goes through normalizer_fn (savp_model.py:380-384).  zw: width of the tiled slice [actions | state | z]."""
-    S.check_norm_layers(hp)
+    handed to the next step -- goes through normalizer_fn (savp_model.py:380-384).  zw: width of the tiled slice [actions | state | z].
+    ln_gru: the opt-in of LayerNormGRU (S.ln_gru_opt_in: None reads SAVP_LN_GRU); without it ('gru', 'layer') is refused."""
+    S.check_norm_layers(hp, ln_gru)
     out_norm = bool(hp.ablation_conv_rnn_norm)
     # The cell WITHOUT a normaliser (ConvLSTM, rnn_ops.py:122-125: the gate convolution then has a bias; ConvGRU, :220-223: both
     # convolutions have one): conv_rnn_norm_layer = 'none', or ablation_conv_rnn_norm
@@ -39,7 +40,8 @@ def cell_class(hp, zw=0):
                                       "the HIP path")
         return BareGRU, out_norm
     if hp.conv_rnn == 'gru':
-        return InstanceNormGRU, False
+        # 'layer' gets here with the opt-in only (check_norm_layers above)
+        return (LayerNormGRU if hp.conv_rnn_norm_layer == 'layer' else InstanceNormGRU), False
     if bare:
         return BareLSTM, out_norm
     return (LayerNormLSTM if hp.conv_rnn_norm_layer == 'layer' else InstanceNormLSTM), False
@@ -289,6 +291,52 @@ class InstanceNormGRU(ConvGRU):
         L, n1 = self.L, self.L['n1']
         self._block('gates_bwd', L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'], drh, L['gates'].g[t], dhprev,
                     n1.dgamma, n1.dbeta)
+
+
+class LayerNormGRU(ConvGRU):
+    """conv_rnn_norm_layer = 'layer' inside the GRU cell (separate_norms, rnn_ops.py:234-267): the gates convolution (no bias), a layer
+    norm each for reset and update (one G = 2 block, parameters gathered per step), the candidate convolution, a layer norm of the
+    candidate, h'.  The norms run inside the chunked two-pass gate blocks of csrc/ln_gru.hip: one code path for every plane size, a
+    per-layer workspace created here, no normalised tensor stored.  Opt-in (S.ln_gru_opt_in)."""
+
+    def __init__(self, gen, L, prefix, out_norm=False):
+        super(LayerNormGRU, self).__init__(gen, L, prefix)
+        f, (h_, w_), r = self.f, L['hw'], self.scope
+        if h_ * w_ > K.GRU_SMALL_MAX_HW and gen.train:
+            # as for InstanceNormGRU: the train step is not pinned against the oracle at such frames (profiles/gru_large.md)
+            raise NotImplementedError("conv_rnn='gru' with its layer norm on a conv-RNN plane of %dx%d = %d pixels (layer h%d, above "
+                                      "%d): mode='train' is not offered at this frame size yet, generation and evaluation are "
+                                      "(profiles/gru_large.md)" % (h_, w_, h_ * w_, L['idx'], K.GRU_SMALL_MAX_HW))
+        # reset / update: one G = 2 launch over the gate tensor
+        L['gn2'] = S.ConcatNorm([S.Norm(gen.store, r + 'gates/' + nm + '/', gen.T1, gen.N, f, gen.dev, groups=1)
+                                 for nm in ('reset', 'update')], gen.T1, gen.N, gen.dev)
+        L['nC'] = S.Norm(gen.store, r + 'candidate/state/', gen.T1, gen.N, f, gen.dev, groups=1)
+        L['ln_gru_ws'] = K.convgru_ln_ws(gen.dev, gen.N, h_ * w_, f)
+
+    def prep(self):
+        self.L['gn2'].prep()
+
+    def gates_fwd(self, t, hprev, rh):
+        L, n1 = self.L, self.L['gn2']
+        K.convgru_ln_gates_fwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['u'][t], rh, L['ln_gru_ws'], eps=K.EPS_LN)
+
+    def out_fwd(self, t, hprev, hdst):
+        L, n2 = self.L, self.L['nC']
+        K.convgru_ln_out_fwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], hdst, L['ln_gru_ws'], eps=K.EPS_LN)
+
+    def out_bwd(self, t, hprev, dys):
+        L, n2 = self.L, self.L['nC']
+        K.convgru_ln_out_bwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], dys, L['cand'].g[t], L['du'],
+                             L['dh_tmp'], n2.dgamma, n2.dbeta, L['ln_gru_ws'], eps=K.EPS_LN)
+
+    def gates_bwd(self, t, hprev, drh, dhprev):
+        L, n1 = self.L, self.L['gn2']
+        K.convgru_ln_gates_bwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'], drh, L['gates'].g[t], dhprev,
+                               n1.dgamma, n1.dbeta, L['ln_gru_ws'], eps=K.EPS_LN)
+
+    def backward_weights(self):
+        super(LayerNormGRU, self).backward_weights()
+        self.L['gn2'].finish()
 
 
 class BareGRU(ConvGRU):

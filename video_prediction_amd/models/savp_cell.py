@@ -31,8 +31,14 @@ NORM_BWD_STATS = os.environ.get('SAVP_NORM_BWD_STATS', '1') == '1'      # ... an
 EPS_IN = 1e-6   # fused_instance_norm epsilon (layers/normalization.py:37)
 
 
-def check_norm_layers(hp):
-    """The normaliser combinations of the HIP path; anything else raises with the combination named."""
+def ln_gru_opt_in(flag=None):
+    """The opt-in of the layer-norm ConvGRU cell (conv_rnn='gru' with conv_rnn_norm_layer='layer', conv_rnn_cells.LayerNormGRU): the
+    keyword where one was given, else SAVP_LN_GRU=1 in the environment, read when called.  Without it the combination stays refused."""
+    return bool(flag) if flag is not None else os.environ.get('SAVP_LN_GRU', '0') == '1'
+
+
+def check_norm_layers(hp, ln_gru=None):
+    """The normaliser combinations of the HIP path; anything else raises with the combination named.  ln_gru: see ln_gru_opt_in."""
     if hp.conv_rnn not in ('lstm', 'gru'):
         raise NotImplementedError("conv_rnn=%r" % hp.conv_rnn)
     if hp.norm_layer not in ('instance', 'layer'):
@@ -47,7 +53,7 @@ def check_norm_layers(hp):
                                   "cancelled by an instance norm" % (hp.norm_layer, hp.conv_rnn_norm_layer))
     if hp.conv_rnn_norm_layer == 'layer' and not hp.ablation_rnn:
         # (under ablation_conv_rnn_norm the cell itself has no normaliser and the layer norm sits on the layer's output: covered)
-        if hp.conv_rnn == 'gru' and not hp.ablation_conv_rnn_norm:
+        if hp.conv_rnn == 'gru' and not hp.ablation_conv_rnn_norm and not ln_gru_opt_in(ln_gru):
             raise NotImplementedError("conv_rnn='gru' with conv_rnn_norm_layer='layer': the GRU gate kernels are instance-norm only")
 
 
@@ -190,7 +196,7 @@ from . import conv_rnn_cells      # noqa: E402  (the cells build on Act, Norm an
 
 
 class SAVPGenerator(object):
-    def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0), pix=0):
+    def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0), pix=0, ln_gru=None):
         """cond = (n_actions, n_states): widths of inputs['actions'] / inputs['states'] (savp_model.py:411-444): [actions_t | state_t]
         joins the latent in every tile-concatenated slice, the next state is predicted by `state_pred/dense` (:655-658).
         pix = P: designated pixels of inputs['pix_distribs'] (:408-410,598-621,648-653); 0 = the model has no such input and nothing below
@@ -203,7 +209,7 @@ class SAVPGenerator(object):
         dev = store.device
         self.dev = dev
         self._cstats = {}                # head name -> the conv's epilogue supplies the instance norm's statistics (decided at first use)
-        check_norm_layers(hp)
+        check_norm_layers(hp, ln_gru)
         # norm_layer = 'layer': every norm_layer site (the ladder's layers, ablation_rnn's conv_h<i>, the 3x3 heads) is a layer norm,
         # variables under <scope>/LayerNorm/ (csrc/group_norm.hip with one group; the heads' merged launch: one group per head)
         self.ln = hp.norm_layer == 'layer'
@@ -261,7 +267,7 @@ class SAVPGenerator(object):
         # those variables keep their (zero-initialised) gradients; pinned against the oracle, which computes the sums literally.
         tile = bool(hp.use_tile_concat)
         # which conv-RNN cell the recurrent layers run (the matrix of DESIGN.md section 1), and whether its output takes a norm of its own
-        cell, out_norm = conv_rnn_cells.cell_class(hp, zw)
+        cell, out_norm = conv_rnn_cells.cell_class(hp, zw, ln_gru)
         zr = zw if (hp.where_add == 'all' and tile) else 0              # tiled channels in a conv-RNN's input [x | actions state z | h]
         g = train
         # bf16 storage of tensors whose ONLY readers are convolutions of the bf16 datapath (round 4; the cell input [x | z | h] and the

@@ -23,7 +23,7 @@ from ..engine import ParamStore, copy_view, add_views
 from .base_model import VideoPredictionModel, learning_rate, kl_weight
 from .hparam_defaults import savp_defaults, SAVP_DEPRECATED_KEYS
 from .networks import PosteriorEncoder, SNDiscriminator
-from .savp_cell import SAVPGenerator, check_kernel_size
+from .savp_cell import SAVPGenerator, check_kernel_size, check_norm_layers, ln_gru_opt_in
 
 
 def _image_shape(images):
@@ -159,7 +159,7 @@ class SAVPEngine(object):
     UNSUPPORTED_WEIGHTS = ('vgg_cdist_weight', 'feature_l2_weight', 'ae_l2_weight')
 
     def __init__(self, hp, image_shape, batch_size, mode='train', values=None, seed=4, device='cuda:0', base_seed=0, rank=0,
-                 cond=(0, 0), lpips_weights=None, pix_distribs=0, store=None, guard=None):
+                 cond=(0, 0), lpips_weights=None, pix_distribs=0, store=None, guard=None, ln_gru=None):
         """store: the ParamStore of another engine to look the variables up in instead of creating them (a mode='test' engine only: the
         long_sequence_length model of scripts/train.py); every name this engine needs must be there with its shape.
         pix_distribs = P: the number of designated pixels of inputs['pix_distribs'] [B, T, H, W, P] (savp_model.py:252-255,408-410,598-621,
@@ -170,8 +170,12 @@ class SAVPEngine(object):
         variable); without one the lpips metric and eval_diversity are not produced.
         guard: skip an optimiser group's Adam update when its gradient holds a non-finite value, and report gradient norms (default: the
         SAVP_GUARD environment variable, '1' = on; off otherwise).  mode='train' only: an inference engine has no gradient and ignores it.
-        Off, the step has no buffer, launch or graph node for it.  See guard_enabled() and _guarded_adam()."""
+        Off, the step has no buffer, launch or graph node for it.  See guard_enabled() and _guarded_adam().
+        ln_gru: the opt-in of the layer-norm ConvGRU cell, conv_rnn='gru' with conv_rnn_norm_layer='layer' (default: the SAVP_LN_GRU
+        environment variable, '1' = on); without it that combination is refused and nothing differs for any other model."""
         self.hp, self.mode, self.B = hp, mode, batch_size
+        self.ln_gru = ln_gru_opt_in(ln_gru)
+        check_norm_layers(hp, self.ln_gru)     # before anything is allocated (the generator checks again)
         bad = [k for k in self.UNSUPPORTED_WEIGHTS if getattr(hp, k, 0)]
         if bad and mode == 'train':
             raise NotImplementedError('loss weights not covered by the HIP path: %s' % ', '.join(bad))
@@ -210,7 +214,7 @@ class SAVPEngine(object):
         self.P = int(pix_distribs or 0)
         if self.P < 0:
             raise ValueError('pix_distribs = %r: the number of designated pixels' % (pix_distribs,))
-        self.gen = SAVPGenerator(store, hp, image_shape, N, train=self.train, cond=self.cond, pix=self.P)
+        self.gen = SAVPGenerator(store, hp, image_shape, N, train=self.train, cond=self.cond, pix=self.P, ln_gru=self.ln_gru)
         # designated-pixel distributions, staged time-major beside the images (sliced to T1 like every input: savp_model.py:690-691)
         self.pix_tm = torch.empty(self.T1, B, H, W, self.P, device=self.device) if self.P else None
         self.pix_n = (torch.empty(self.T1, N, H, W, self.P, device=self.device) if self.nz else self.pix_tm) if self.P else None
@@ -1161,7 +1165,7 @@ class _ParallelPriorEval(object):
         T, T1, nz = eng.T, eng.T1, eng.nz
         self.F = F = T - hp.context_frames
         self.c1 = hp.context_frames - 1
-        self.gen = SAVPGenerator(eng.net_store, hp, eng.image_shape, N, train=False, cond=eng.cond)
+        self.gen = SAVPGenerator(eng.net_store, hp, eng.image_shape, N, train=False, cond=eng.cond, ln_gru=eng.ln_gru)
         self.images = torch.empty(T, N, H, W, C, device=dev)
         self.zs = torch.zeros(T1, N, nz, device=dev)
         gt = torch.zeros(T1, N, dtype=torch.int32)
@@ -1514,6 +1518,8 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         self.pix_distribs = pix_distribs_opt_in(kwargs.pop('pix_distribs', None))
         # skip Adam updates on non-finite gradients and report gradient norms (guard=True, or SAVP_GUARD=1); ignored by a mode='test' model
         guard = kwargs.pop('guard', None)
+        # opt-in of the layer-norm ConvGRU cell (ln_gru=True, or SAVP_LN_GRU=1); without it conv_rnn='gru' + conv_rnn_norm_layer='layer' is refused
+        self.ln_gru = ln_gru_opt_in(kwargs.pop('ln_gru', None))
         super(SAVPVideoPredictionModel, self).__init__(generator_fn, discriminator_fn, *args, **kwargs)
         if self.mode != 'train':
             self.discriminator_fn = None
@@ -1556,7 +1562,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         B = images.shape[0]
         self.engine = SAVPEngine(self.hparams, tuple(images.shape[2:]), B, mode=self.mode, values=values, seed=seed,
                                  device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights, pix_distribs=P, store=store,
-                                 guard=self.guard)
+                                 guard=self.guard, ln_gru=self.ln_gru)
         self.saveable_variables = self.engine.store.names()
         self.post_init_ops = []
         self.outputs = {}

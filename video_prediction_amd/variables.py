@@ -204,6 +204,12 @@ def generator_variable_specs(hp, image_shape, cond=(0, 0)):
             if not cell_norm:
                 specs[s + 'gates/bias'] = ((2 * f,), 'ones')
                 specs[s + 'candidate/bias'] = ((f,), 'zeros')
+            elif hp.conv_rnn_norm_layer == 'layer':
+                # separate_norms (rnn_ops.py:203-212,244-256): reset, update and the candidate normalised on their own, the cell's _norm
+                # creates <scope>/{gamma,beta} (no LayerNorm level); bias_ones: beta of the two gates starts at one
+                for name, beta in (('gates/reset', 'ones'), ('gates/update', 'ones'), ('candidate/state', 'zeros')):
+                    specs[s + name + '/gamma'] = ((f,), 'ones')
+                    specs[s + name + '/beta'] = ((f,), beta)
             else:
                 specs[s + 'gates/reset_update/gamma'] = ((2 * f,), 'ones')
                 specs[s + 'gates/reset_update/beta'] = ((2 * f,), 'ones')
