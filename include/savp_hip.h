@@ -41,7 +41,10 @@ const char* savp_version(void);
  * "ring_fixed" 1: a ring-kernel call whose planned geometry equals, in every folded value, one of the train step's recurring problems
  * (csrc/conv_ring_fixed.h) runs that problem's instantiation of the same kernel body with the geometry as compile-time constants; 0: the
  * generic ring kernel everywhere, same bits.  "ring_fixed_taken" is a counter, not a switch: ring launches so far that took a fixed
- * instantiation; set it to 0 to reset. */
+ * instantiation; set it to 0 to reset.
+ * "fd_fixed" 1: the same for the implicit-GEMM FPROP / DGRAD kernel (csrc/conv_fd_fixed.h: the discriminators' 3-D ladder, its data
+ * gradients, the dense data gradient of every generator time step); 0: conv_fd_kernel everywhere, same bits.  "fd_fixed_taken" counts the
+ * launches that took a fixed instantiation; set it to 0 to reset. */
 int savp_set_option(const char* name, int32_t value);
 int savp_get_option(const char* name, int32_t* value);
 
@@ -189,6 +192,15 @@ int64_t savp_conv_workspace_bytes(const SavpConvArgs* args);
 /* 1 when, with tile bits 8-9 == 0 (automatic algorithm), a problem-specific kernel takes this call and tile / splitk are not
  * looked at (a tuner can skip its search); 0 otherwise */
 int savp_conv_special(const SavpConvArgs* args);
+/* The fixed-problem table of the implicit-GEMM FPROP / DGRAD kernel (csrc/conv_fd_fixed.h, option "fd_fixed"), for tests and tools; no
+ * launch, no device access.  savp_fd_fixed_probe writes up to n values of entry `id` to out and returns how many the entry has
+ * (SAVP_EINVAL for an unknown id / what).  what 0: the table line -- mode, N, D, H, W, Cx, Do, Ho, Wo, Cy, kd, kh, kw, sd, sh, sw, pd, ph,
+ * pw, WM, WN, split-K, instantiation bits (1 vector loads, 2 bf16, 4 bf16 weight copy), rank of the tensor views (5, 4 or 2).  what 1: what the launcher's planner gives NOW for
+ * the call the line stands for: mode ... pw, split-K, tile counts tm / tn, bf16, the eight strides (x then y: n, d, h, w), then WM, WN,
+ * output phases, and 1 if the planner keeps the line's tile and split count.  what 2: the same values as the entry's kernel has them
+ * folded at compile time. */
+int savp_fd_fixed_count(void);
+int savp_fd_fixed_probe(int32_t id, int32_t what, int64_t* out, int32_t n);
 
 
 /* A channels-last activation view addressed as p[n*sn + pixel*sp + c] (pixel = flattened D*H*W index; valid for

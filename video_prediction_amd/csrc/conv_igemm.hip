@@ -24,335 +24,19 @@
 #include "zero_fill.h"
 
 #include "conv_common.h"
+#include "conv_fd_kernel.h"
+#include "conv_fd_fixed.h"
 #include <stdlib.h>
+#include <stdio.h>
 
 // ------------------------------------------------------------------------------------------------------------
 // FPROP / DGRAD kernel.  GEMM: C[M = grid pixels][N = dst channels] = A[M][K=(taps,Cred)] * B[K][N]
 // ------------------------------------------------------------------------------------------------------------
-// BF16 = true: operands are rounded to bf16 (RNE, v_cvt_pk_bf16_f32) while staging into LDS and multiplied on
-// v_mfma_f32_32x32x16_bf16 (fp32 accumulate); K-tile 64.  BF16 = false: exact fp32 on v_mfma_f32_32x32x2_f32; K-tile 32.
-// WB16 = true (bf16 mode only): the weight operand is read from a pre-packed bf16 copy (16-byte loads of 8 k values,
-// no conversion, half the L2 traffic and staging instructions of the fp32 stream).
+// The body lives in conv_fd_kernel.h: conv_fd_fixed_*.hip instantiate it a second time with the geometry of the train step's recurring
+// problems folded at compile time (conv_fd_fixed.h).
 template <int WM, int WN, bool VEC, bool BF16, bool WB16>
 __global__ __launch_bounds__(NTHREADS) void conv_fd_kernel(ConvP p) {
-    constexpr int BM = 64 * WM, BN = 64 * WN;
-    constexpr int BKT = BF16 ? 64 : 32;                // K-tile
-    constexpr int KV = BKT / 4;                        // float4 columns per row
-    constexpr int RP = NTHREADS / KV;                  // rows covered per pass
-    constexpr int RA = BM / RP, RB = BN / RP;          // float4 rows fetched per thread for A / B
-    constexpr int ROWB = BF16 ? (BKT + 8) * 2 : BKP * 4;   // LDS row stride in bytes (padded: conflict-free b128 reads)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    char* As = reinterpret_cast<char*>(smem);          // [2][BM] rows
-    char* Bs = As + 2 * BM * ROWB;                     // [2][BN] rows
-
-    const bool dgrad = (p.mode == SAVP_CONV_DGRAD);
-    // blockIdx.z = phase * splitk + split ; phase decode (DGRAD only) -> (fd, fh, fw)
-    const int split = blockIdx.z % p.splitk;
-    int fz = blockIdx.z / p.splitk;
-    int fw = dgrad ? fz % p.sw : 0; fz = dgrad ? fz / p.sw : 0;
-    int fh = dgrad ? fz % p.sh : 0; fz = dgrad ? fz / p.sh : 0;
-    int fd = fz;
-    const DimGeom gd = make_geom(dgrad, fd, p.D, p.Do, p.kd, p.sd, p.pd);
-    const DimGeom gh = make_geom(dgrad, fh, p.H, p.Ho, p.kh, p.sh, p.ph);
-    const DimGeom gw = make_geom(dgrad, fw, p.W, p.Wo, p.kw, p.sw, p.pw);
-
-    const int Cred = dgrad ? p.Cy : p.Cx;             // reduction channels
-    const int Nout = dgrad ? p.Cx : p.Cy;             // destination channels
-    const int ntaps = gd.nt * gh.nt * gw.nt;
-    const int K = ntaps * Cred;
-    const int ldb = p.kd * p.kh * p.kw * Cred;        // packed weight row length
-    const int Mtot = p.N * gd.Mdim * gh.Mdim * gw.Mdim;
-    // logical tile id: n-tile major so that the tiles sharing a weight block are consecutive (-> same XCD L2)
-    const int tlog = xcd_logical(blockIdx.x, p.tm * p.tn);
-    const int m0 = (tlog % p.tm) * BM;
-    const int n0 = (tlog / p.tm) * BN;
-    if (m0 >= Mtot) return;                            // uniform per workgroup (phase with fewer pixels)
-
-    const float* __restrict__ src = dgrad ? p.y : p.x;
-    const long long s_sn = dgrad ? p.y_sn : p.x_sn;
-    const int s_sd = (int)(dgrad ? p.y_sd : p.x_sd), s_sh = (int)(dgrad ? p.y_sh : p.x_sh),
-              s_sw = (int)(dgrad ? p.y_sw : p.x_sw);
-    const float* __restrict__ wt = p.w;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int kv = tid % KV, r0 = tid / KV;
-
-    // ---- per-thread A rows --------------------------------------------------------------------------------
-    long long a_base[RA];
-    int a_cd[RA], a_ch[RA], a_cw[RA];
-    bool a_ok[RA];
-#pragma unroll
-    for (int j = 0; j < RA; ++j) {
-        int m = m0 + r0 + RP * j;
-        a_ok[j] = m < Mtot;
-        int mm = a_ok[j] ? m : 0;
-        int qw = mm % gw.Mdim; mm /= gw.Mdim;
-        int qh = mm % gh.Mdim; mm /= gh.Mdim;
-        int qd = mm % gd.Mdim; int n = mm / gd.Mdim;
-        a_base[j] = (long long)n * s_sn;
-        a_cd[j] = gd.base + qd * gd.mstep;
-        a_ch[j] = gh.base + qh * gh.mstep;
-        a_cw[j] = gw.base + qw * gw.mstep;
-    }
-    // ---- per-thread B rows --------------------------------------------------------------------------------
-    bool b_ok[RB];
-    long long b_base[RB];
-#pragma unroll
-    for (int j = 0; j < RB; ++j) {
-        int n = n0 + r0 + RP * j;
-        b_ok[j] = n < Nout;
-        b_base[j] = (long long)(b_ok[j] ? n : 0) * ldb;
-    }
-    // ---- K state (vector path): this thread's float4 sits at k = kt*32 + kv*4 -------------------------------
-    // split-K: this workgroup reduces K-tiles [kt_begin, kt_end)
-    const int nk_all = (K + BKT - 1) / BKT;
-    const int kt_per = (nk_all + p.splitk - 1) / p.splitk;
-    const int kt_begin = split * kt_per;
-    const int kt_end = min(nk_all, kt_begin + kt_per);
-    int kc = 0, jd = 0, jh = 0, jw = 0;     // channel offset, reduced tap indices
-    if (VEC) {
-        int k = kt_begin * BKT + kv * 4;
-        kc = k % Cred; int tap = k / Cred;
-        jw = tap % max(gw.nt, 1); tap /= max(gw.nt, 1);
-        jh = tap % max(gh.nt, 1); jd = tap / max(gh.nt, 1);
-    }
-
-    float4 ra[RA], rb[RB];
-    // bf16 weight stream: thread -> (row r0b + 32*j, 8-wide k chunk kvb)
-    constexpr int RB16 = BN / 32;
-    const int kvb = tid & 7, r0b = tid >> 3;
-    uint4 rb16[WB16 ? RB16 : 1];
-    long long bb16[WB16 ? RB16 : 1];
-    bool bok16[WB16 ? RB16 : 1];
-    int kcb = 0, jdb = 0, jhb = 0, jwb = 0;
-    if (WB16) {
-#pragma unroll
-        for (int j = 0; j < RB16; ++j) {
-            int n = n0 + r0b + 32 * j;
-            bok16[j] = n < Nout;
-            bb16[j] = (long long)(bok16[j] ? n : 0) * ldb;
-        }
-        int k = kt_begin * BKT + kvb * 8;
-        kcb = k % Cred; int tap = k / Cred;
-        jwb = tap % max(gw.nt, 1); tap /= max(gw.nt, 1);
-        jhb = tap % max(gh.nt, 1); jdb = tap / max(gh.nt, 1);
-    }
-
-    auto fetch = [&](int kt) {
-        if (WB16) {
-            const bool kokb = (jdb < gd.nt) && (ntaps > 0);
-            const int ta = gd.t0 + jdb * gd.tstep, tu = gh.t0 + jhb * gh.tstep, tv = gw.t0 + jwb * gw.tstep;
-            const long long woff = (long long)((ta * p.kh + tu) * p.kw + tv) * Cred + kcb;
-#pragma unroll
-            for (int j = 0; j < RB16; ++j) {
-                const bool ok = bok16[j] && kokb;
-                uint4 v = *reinterpret_cast<const uint4*>(p.w16 + (ok ? bb16[j] + woff : 0ll));
-                rb16[j] = ok ? v : make_uint4(0u, 0u, 0u, 0u);
-            }
-            kcb += BKT;
-            while (kcb >= Cred) {
-                kcb -= Cred;
-                if (++jwb >= gw.nt) { jwb = 0; if (++jhb >= gh.nt) { jhb = 0; ++jdb; } }
-            }
-        }
-        if (VEC) {
-            const bool kok = (jd < gd.nt) && (ntaps > 0);
-            const int zd0 = jd * gd.jstep, zh0 = jh * gh.jstep, zw0 = jw * gw.jstep;
-#pragma unroll
-            for (int j = 0; j < RA; ++j) {
-                int zd = a_cd[j] + zd0, zh = a_ch[j] + zh0, zw = a_cw[j] + zw0;
-                bool ok = a_ok[j] && kok && (unsigned)zd < (unsigned)gd.srcN && (unsigned)zh < (unsigned)gh.srcN &&
-                          (unsigned)zw < (unsigned)gw.srcN;
-                // branch-free: out-of-image taps read a safe address and are zeroed by a select, so all gathers of a K-tile
-                // are issued back to back (a branch per load serialised them and cost an s_cbranch each)
-                const long long off = ok ? (a_base[j] + (long long)zd * s_sd + (long long)zh * s_sh + (long long)zw * s_sw + kc) : 0ll;
-                float4 v = ldg4(src + off);
-                ra[j] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            const int ta = gd.t0 + jd * gd.tstep, tu = gh.t0 + jh * gh.tstep, tv = gw.t0 + jw * gw.tstep;
-            const long long woff = (long long)((ta * p.kh + tu) * p.kw + tv) * Cred + kc;
-            if (!WB16) {
-#pragma unroll
-                for (int j = 0; j < RB; ++j) {
-                    const bool ok = b_ok[j] && kok;
-                    float4 v = ldg4(wt + (ok ? b_base[j] + woff : 0ll));
-                    rb[j] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            }
-            // advance by the K-tile
-            kc += BKT;
-            while (kc >= Cred) {
-                kc -= Cred;
-                if (++jw >= gw.nt) { jw = 0; if (++jh >= gh.nt) { jh = 0; ++jd; } }
-            }
-        } else {
-            // scalar path: arbitrary Cred (first layers with 3/6/14 channels, the 53-channel mask conv)
-            float av[RA][4], bv[RB][4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int k = kt * BKT + kv * 4 + e;
-                bool kok = k < K;
-                int kk = kok ? k : 0;
-                int c = kk % Cred; int tap = kk / Cred;
-                int tw_ = tap % max(gw.nt, 1); tap /= max(gw.nt, 1);
-                int th_ = tap % max(gh.nt, 1); int td_ = tap / max(gh.nt, 1);
-#pragma unroll
-                for (int j = 0; j < RA; ++j) {
-                    int zd = a_cd[j] + td_ * gd.jstep, zh = a_ch[j] + th_ * gh.jstep, zw = a_cw[j] + tw_ * gw.jstep;
-                    bool ok = a_ok[j] && kok && (unsigned)zd < (unsigned)gd.srcN && (unsigned)zh < (unsigned)gh.srcN &&
-                              (unsigned)zw < (unsigned)gw.srcN;
-                    av[j][e] = ok ? src[a_base[j] + (long long)zd * s_sd + (long long)zh * s_sh + (long long)zw * s_sw + c] : 0.f;
-                }
-                int ta = gd.t0 + td_ * gd.tstep, tu = gh.t0 + th_ * gh.tstep, tv = gw.t0 + tw_ * gw.tstep;
-                long long woff = (long long)((ta * p.kh + tu) * p.kw + tv) * Cred + c;
-#pragma unroll
-                for (int j = 0; j < RB; ++j) bv[j][e] = (b_ok[j] && kok) ? wt[b_base[j] + woff] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < RA; ++j) ra[j] = make_float4(av[j][0], av[j][1], av[j][2], av[j][3]);
-#pragma unroll
-            for (int j = 0; j < RB; ++j) rb[j] = make_float4(bv[j][0], bv[j][1], bv[j][2], bv[j][3]);
-        }
-    };
-    auto stage = [&](int buf) {
-        char* a = As + buf * BM * ROWB;
-        char* b = Bs + buf * BN * ROWB;
-        if (BF16) {
-#pragma unroll
-            for (int j = 0; j < RA; ++j) {
-                bf16x4 v = {(__bf16)ra[j].x, (__bf16)ra[j].y, (__bf16)ra[j].z, (__bf16)ra[j].w};
-                *reinterpret_cast<bf16x4*>(a + (r0 + RP * j) * ROWB + kv * 8) = v;
-            }
-            if (WB16) {
-#pragma unroll
-                for (int j = 0; j < RB16; ++j) *reinterpret_cast<uint4*>(b + (r0b + 32 * j) * ROWB + kvb * 16) = rb16[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < RB; ++j) {
-                    bf16x4 v = {(__bf16)rb[j].x, (__bf16)rb[j].y, (__bf16)rb[j].z, (__bf16)rb[j].w};
-                    *reinterpret_cast<bf16x4*>(b + (r0 + RP * j) * ROWB + kv * 8) = v;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < RA; ++j) *reinterpret_cast<float4*>(a + (r0 + RP * j) * ROWB + kv * 16) = ra[j];
-#pragma unroll
-            for (int j = 0; j < RB; ++j) *reinterpret_cast<float4*>(b + (r0 + RP * j) * ROWB + kv * 16) = rb[j];
-        }
-    };
-
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int wm0 = (wave >> 1) * 32 * WM, wn0 = (wave & 1) * 32 * WN;
-    const int l31 = lane & 31, khalf = lane >> 5;
-    // software pipeline: LDS holds tile kt (cur) while the registers hold tile kt+1 whose global loads were issued one
-    // whole iteration earlier (right after the previous stage), so they fly under a barrier + a full MFMA block.
-    if (kt_begin < kt_end) {
-        fetch(kt_begin);
-        stage(0);
-        if (kt_begin + 1 < kt_end) fetch(kt_begin + 1);
-    }
-    __syncthreads();
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-        const int cur = (kt - kt_begin) & 1;
-        const char* a = As + cur * BM * ROWB;
-        const char* b = Bs + cur * BN * ROWB;
-        if (BF16) {
-#pragma unroll
-            for (int ks = 0; ks < BKT / 16; ++ks) {
-                bf16x8 af[WM], bf[WN];
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-                    af[i] = *reinterpret_cast<const bf16x8*>(a + (wm0 + i * 32 + l31) * ROWB + (ks * 16 + khalf * 8) * 2);
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-                    bf[j] = *reinterpret_cast<const bf16x8*>(b + (wn0 + j * 32 + l31) * ROWB + (ks * 16 + khalf * 8) * 2);
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < WN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int c8 = 0; c8 < BKT / 8; ++c8) {
-                float4 af[WM], bf[WN];
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-                    af[i] = *reinterpret_cast<const float4*>(a + (wm0 + i * 32 + l31) * ROWB + (c8 * 8 + khalf * 4) * 4);
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-                    bf[j] = *reinterpret_cast<const float4*>(b + (wn0 + j * 32 + l31) * ROWB + (c8 * 8 + khalf * 4) * 4);
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < WN; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].x, bf[j].x, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].y, bf[j].y, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].z, bf[j].z, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].w, bf[j].w, acc[i][j], 0, 0, 0);
-                    }
-            }
-        }
-        if (kt + 1 < kt_end) {
-            stage(cur ^ 1);
-            if (kt + 2 < kt_end) fetch(kt + 2);
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue: destination row offsets through LDS -------------------------------------------------------
-    long long* rowoff = reinterpret_cast<long long*>(smem);     // [BM], -1 = invalid (safe: last barrier of the loop passed)
-    float* __restrict__ dst = p.out;
-    const long long d_sn = dgrad ? p.x_sn : p.y_sn;
-    const long long d_sd = dgrad ? p.x_sd : p.y_sd, d_sh = dgrad ? p.x_sh : p.y_sh, d_sw = dgrad ? p.x_sw : p.y_sw;
-    if (tid < BM) {
-        int m = m0 + tid;
-        long long off = -1;
-        if (m < Mtot) {
-            int mm = m;
-            int qw = mm % gw.Mdim; mm /= gw.Mdim;
-            int qh = mm % gh.Mdim; mm /= gh.Mdim;
-            int qd = mm % gd.Mdim; int n = mm / gd.Mdim;
-            off = (long long)n * d_sn + (long long)(gd.ob + qd * gd.os) * d_sd + (long long)(gh.ob + qh * gh.os) * d_sh +
-                  (long long)(gw.ob + qw * gw.os) * d_sw;
-        }
-        rowoff[tid] = off;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-        const int col = n0 + wn0 + j * 32 + l31;
-        if (col >= Nout) continue;
-        const float bias = (p.bias && split == 0) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                const long long off = rowoff[row];
-                if (off < 0) continue;
-                float v = acc[i][j][r] + bias;
-                float* q = dst + off + col;
-                if (p.splitk > 1) {               // this split's share (conv_common.h: deterministic split-K)
-                    (p.part + (long long)split * p.part_sz + (dst - p.out))[off + col] = v;
-                    continue;
-                }
-                if (p.beta) v += *q;
-                if (p.act == SAVP_ACT_LRELU) v = fmaxf(v, p.alpha * v);
-                else if (p.act == SAVP_ACT_SIGMOID) v = 1.f / (1.f + __expf(-v));
-                else if (p.act == SAVP_ACT_DLRELU_FROM_OUT) v *= (p.aux[off + col] > 0.f ? 1.f : p.alpha);
-                *q = v;
-            }
-        }
-    }
+    conv_fd_body<WM, WN, VEC, BF16, WB16>(p);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -720,11 +404,17 @@ static hipError_t launch_fd1(const ConvP& p, dim3 grid, hipStream_t st) {
     return hipGetLastError();
 }
 
+// the instantiation a call takes, as conv_fd_fixed.h's FD_* bits
+static int fd_flags(const ConvP& p, bool vec) {
+    if (p.bf16 && vec && p.w16) return FD_VEC | FD_BF16 | FD_WB16;
+    return (vec ? FD_VEC : 0) | (p.bf16 ? FD_BF16 : 0);
+}
+
 template <int WM, int WN>
-static hipError_t launch_fd(const ConvP& p, bool vec, dim3 grid, hipStream_t st) {
-    if (p.bf16 && vec && p.w16) return launch_fd1<WM, WN, true, true, true>(p, grid, st);
-    if (p.bf16) return vec ? launch_fd1<WM, WN, true, true>(p, grid, st) : launch_fd1<WM, WN, false, true>(p, grid, st);
-    return vec ? launch_fd1<WM, WN, true, false>(p, grid, st) : launch_fd1<WM, WN, false, false>(p, grid, st);
+static hipError_t launch_fd(const ConvP& p, int flags, dim3 grid, hipStream_t st) {
+    if (flags == (FD_VEC | FD_BF16 | FD_WB16)) return launch_fd1<WM, WN, true, true, true>(p, grid, st);
+    if (flags & FD_BF16) return (flags & FD_VEC) ? launch_fd1<WM, WN, true, true>(p, grid, st) : launch_fd1<WM, WN, false, true>(p, grid, st);
+    return (flags & FD_VEC) ? launch_fd1<WM, WN, true, false>(p, grid, st) : launch_fd1<WM, WN, false, false>(p, grid, st);
 }
 
 template <int WM, int WN>
@@ -744,21 +434,6 @@ static hipError_t launch_wg(const ConvP& p, bool va, bool vb, dim3 grid, hipStre
     return hipGetLastError();
 }
 
-
-static void pick_tile(long long M, long long N, int& wm, int& wn) {
-    // cost model: rounds over the 256 CUs x tile area x a re-read penalty for small tiles
-    const int opts[4][2] = {{2, 2}, {2, 1}, {1, 2}, {1, 1}};
-    double best = 1e300;
-    for (int i = 0; i < 4; ++i) {
-        long long bm = 64 * opts[i][0], bn = 64 * opts[i][1];
-        long long tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
-        double wgs = (double)tm * tn;
-        double rounds = wgs <= 256.0 ? 1.0 : wgs / 256.0;
-        double eff = (bm * bn == 128 * 128) ? 1.0 : (bm * bn == 64 * 64 ? 1.3 : 1.12);
-        double cost = rounds * (double)(bm * bn) * eff;
-        if (cost < best) { best = cost; wm = opts[i][0]; wn = opts[i][1]; }
-    }
-}
 
 // auto algorithm choice between the two LDS-patch kernels when the caller gives no tile: SAVP_CONV_RING=1 prefers conv_ring.hip
 static bool ring_default() {
@@ -950,45 +625,41 @@ extern "C" int savp_conv(void* stream, const SavpConvArgs* a) {
             if (conv_patch_try(p, a, wm, wn, algo == 2, st, &rc)) return rc;
             if (algo == 2) return SAVP_EINVAL;
         }
-        if (!wm) pick_tile(Mmax * phases, Nout, wm, wn);
-        const int BM = 64 * wm, BN = 64 * wn;
-        // split-K (plain epilogue only): fills the chip when M*N is small and K is long (8x8 / 16x16 ConvLSTM layers)
-        int splitk = a->splitk;
-        const long long tiles = ((Mmax + BM - 1) / BM) * ((Nout + BN - 1) / BN) * phases;
-        const long long taps_max = (long long)a->kd * a->kh * a->kw / (dg ? phases : 1);
-        const long long nkt = (taps_max * Cred + (p.bf16 ? 63 : 31)) / (p.bf16 ? 64 : 32);
-        const bool can_split = (a->act == SAVP_ACT_NONE);
-        if (!can_split) splitk = 1;
-        else if (splitk <= 0) {
-            splitk = 1;
-            if (tiles <= 192 && nkt >= 16) {
-                long long s1 = 512 / tiles, s2 = nkt / 8;
-                splitk = (int)(s1 < s2 ? s1 : s2);
-                if (splitk < 1) splitk = 1;
-                if (splitk > 16) splitk = 16;
-            }
-        }
-        if (splitk > 1) {
-            // the destination must be one dense block: split s stores its share at the same offsets of its slice of the scratch
-            const long long dD = dg ? a->D : a->Do, dH = dg ? a->H : a->Ho, dW_ = dg ? a->W : a->Wo;
-            const long long s_n = dg ? a->x_sn : a->y_sn, s_d = dg ? a->x_sd : a->y_sd, s_h = dg ? a->x_sh : a->y_sh,
-                            s_w = dg ? a->x_sw : a->y_sw;
-            const bool dense = (s_w == Nout) && (s_h == dW_ * Nout) && (dD == 1 || s_d == dH * dW_ * Nout) &&
-                               (s_n == dD * dH * dW_ * Nout);
-            if (!dense) splitk = 1;
-            else {
-                p.part_sz = (long long)a->N * dD * dH * dW_ * Nout;
-                splitk = splitk_fit(a, splitk, p.part_sz);
-                p.part = (float*)a->ws;
-            }
+        // tile, tile counts and the split count the call asks for: constexpr code shared with the fixed-problem table (conv_fd_fixed.h)
+        FdPlan g{};
+        fd_plan(a, p.bf16 != 0, wm, wn, g);
+        wm = g.wm; wn = g.wn;
+        int splitk = g.splitk;
+        if (splitk > 1) {                                  // (a dense destination: fd_plan) as many slices as the caller's scratch holds
+            p.part_sz = g.part_sz;
+            splitk = splitk_fit(a, splitk, p.part_sz);
+            p.part = (float*)a->ws;
         }
         p.splitk = splitk;
-        p.tm = (int)((Mmax + BM - 1) / BM); p.tn = (int)((Nout + BN - 1) / BN);
+        p.tm = g.tm; p.tn = g.tn;
         dim3 grid((unsigned)(p.tm * p.tn), 1, (unsigned)(phases * splitk));
-        if (wm == 2 && wn == 2) err = launch_fd<2, 2>(p, vec, grid, st);
-        else if (wm == 2 && wn == 1) err = launch_fd<2, 1>(p, vec, grid, st);
-        else if (wm == 1 && wn == 2) err = launch_fd<1, 2>(p, vec, grid, st);
-        else err = launch_fd<1, 1>(p, vec, grid, st);
+        const int flags = fd_flags(p, vec);
+        // option "fd_fixed": a call whose planned geometry equals a fixed problem's in every folded value runs that problem's instantiation
+        // (same body, geometry as compile-time constants, conv_fd_fixed.h); every other call the generic kernel
+        const int fixed = savp_opt(OPT_FD_FIXED) ? fd_fixed_find(p, wm, wn, flags, phases) : -1;
+#ifdef SAVP_FD_LOG
+        // developer build: one line per launch -- the planned problem as the table of conv_fd_fixed.h lists it, the call site's strides and
+        // epilogue switches, and the entry it matched (tests/tools/fd_problems.py counts the distinct lines of a step)
+        fprintf(stderr, "FDLOG {%d, %d, %d, %d, %d, %d, %d, %d, %d, %d,  %d, %d, %d, %d, %d, %d, %d, %d, %d,  %d, %d, %d, %d, %d} beta=%d act=%d alpha=%g bias=%d "
+                "aux=%d xs=%lld,%lld,%lld,%lld ys=%lld,%lld,%lld,%lld atile=0x%x asplitk=%d fixed=%d\n",
+                p.mode, p.N, p.D, p.H, p.W, p.Cx, p.Do, p.Ho, p.Wo, p.Cy, p.kd, p.kh, p.kw, p.sd, p.sh, p.sw, p.pd, p.ph, p.pw, wm, wn, splitk, flags,
+                (p.x_sd || p.y_sd) ? 5 : ((p.x_sw || p.y_sw) ? 4 : 2),     // rank of the views, as a table line states it
+                p.beta, p.act, (double)p.alpha, p.bias != nullptr, p.aux != nullptr, p.x_sn, p.x_sd, p.x_sh, p.x_sw, p.y_sn, p.y_sd, p.y_sh, p.y_sw,
+                a->tile, a->splitk, fixed);
+#endif
+        if (fixed >= 0) {
+            savp_opt_count(OPT_FD_FIXED_TAKEN);
+            err = fixed % 2 == 0 ? fd_fixed_launch_a(fixed, p, grid, st) : fd_fixed_launch_b(fixed, p, grid, st);
+        }
+        else if (wm == 2 && wn == 2) err = launch_fd<2, 2>(p, flags, grid, st);
+        else if (wm == 2 && wn == 1) err = launch_fd<2, 1>(p, flags, grid, st);
+        else if (wm == 1 && wn == 2) err = launch_fd<1, 2>(p, flags, grid, st);
+        else err = launch_fd<1, 1>(p, flags, grid, st);
         if (splitk > 1 && err == hipSuccess) {
             splitk_fold(p.out, p.part, splitk, p.part_sz, a->beta, Nout, 0, 0, st);
             err = hipGetLastError();
@@ -1047,4 +718,43 @@ extern "C" int savp_conv(void* stream, const SavpConvArgs* a) {
         return SAVP_EINVAL;
     }
     return err == hipSuccess ? SAVP_OK : SAVP_ELAUNCH;
+}
+
+// ---- the fixed-problem table of conv_fd_fixed.h, for tests and tools (include/savp_hip.h) --------------------------------------------------
+extern "C" int savp_fd_fixed_count(void) { return kFdFixedCount; }
+
+extern "C" int savp_fd_fixed_probe(int id, int what, int64_t* out, int n) {
+    if (id < 0 || id >= kFdFixedCount || !out || n < 0) return SAVP_EINVAL;
+    const FdFixedDesc& d = kFdFixed[id];
+    int k = 0;
+    if (what == 0) {                                       // the table line
+        const int v[] = {d.mode, d.N, d.D, d.H, d.W, d.Cx, d.Do, d.Ho, d.Wo, d.Cy, d.kd, d.kh, d.kw, d.sd, d.sh, d.sw, d.pd, d.ph, d.pw, d.wm, d.wn, d.splitk, d.flags, d.rank};
+        for (int x : v) { if (k < n) out[k] = x; ++k; }
+        return k;
+    }
+    if (what == 1) {                                       // the planner, run now, on the call the line stands for
+        const SavpConvArgs a = fd_fixed_args(d);
+        ConvP p{};
+        FdPlan g{};
+        fd_plan(&a, a.precision == SAVP_PREC_BF16, (a.tile >> 4) & 15, a.tile & 15, g);
+        fd_geometry_fields(p, &a, g);
+        p.bf16 = a.precision == SAVP_PREC_BF16 ? 1 : 0;
+#define F(T, f) if (k < n) out[k] = (long long)p.f; ++k;
+        FD_FIXED_FIELDS(F)
+#undef F
+        const long long tail[] = {g.wm, g.wn, g.phases, kFdFixedTab.e[id].ok ? 1 : 0};
+        for (long long x : tail) { if (k < n) out[k] = x; ++k; }
+        return k;
+    }
+    if (what == 2) {                                       // what FdFixedP<id> folds, then the entry's tile, phases and ok flag
+        long long tmp[64];
+        k = id % 2 == 0 ? fd_fixed_folded_a(id, tmp, 64) : fd_fixed_folded_b(id, tmp, 64);
+        if (k < 0) return SAVP_EINVAL;
+        for (int i = 0; i < k && i < n; ++i) out[i] = tmp[i];
+        const FdFixedEntry& e = kFdFixedTab.e[id];
+        const long long tail[] = {e.wm, e.wn, e.phases, e.ok ? 1 : 0};
+        for (long long x : tail) { if (k < n) out[k] = x; ++k; }
+        return k;
+    }
+    return SAVP_EINVAL;
 }

@@ -28,6 +28,8 @@ enum SavpOptId {
     OPT_SPLITK_REDUCED,    // counter, not a switch: calls whose requested split-K count was cut (or dropped) because the caller's scratch was too small
     OPT_RING_FIXED,        // ring kernel: a call whose planned geometry equals a fixed problem's (conv_ring_fixed.h) runs that problem's instantiation, geometry folded at compile time (1; 0: conv_ring_kernel everywhere, same bits)
     OPT_RING_FIXED_TAKEN,  // counter, not a switch: ring launches that took a fixed instantiation so far
+    OPT_FD_FIXED,          // implicit-GEMM FPROP / DGRAD kernel: a call whose planned geometry equals a fixed problem's (conv_fd_fixed.h) runs that problem's instantiation, geometry folded at compile time (1; 0: conv_fd_kernel everywhere, same bits)
+    OPT_FD_FIXED_TAKEN,    // counter, not a switch: implicit-GEMM launches that took a fixed instantiation so far
     OPT_COUNT
 };
 

@@ -103,7 +103,7 @@ class _LdsPoisonProxy(object):
 # for A/B runs the host forwards SAVP_<NAME>=<int> here, once, when the library is loaded.  'inorm_fast_taken', 'splitk_reduced' and 'ring_fixed_taken' are counters the library
 # increments, not switches: they are in the list to be read (and reset to 0) through get_option / set_option, not to be set from the environment.
 OPTION_NAMES = ('conv_ring', 's2dgrad', 'thin', 'wgp_cfg', 'wgp_split', 'inorm_min_hw', 'colsum_2stage', 'dense_legacy', 'cdna_legacy',
-                'lstm_fused', 'ring_dma', 'lstm_q', 'ring_wwarm', 'wgp_dma', 'ring_early', 'gate_kernel', 'gate_alt', 'gate_cell', 'gate_wwarm', 'inorm_fast', 'inorm_fast_taken', 'splitk_reduced', 'ring_fixed', 'ring_fixed_taken')
+                'lstm_fused', 'ring_dma', 'lstm_q', 'ring_wwarm', 'wgp_dma', 'ring_early', 'gate_kernel', 'gate_alt', 'gate_cell', 'gate_wwarm', 'inorm_fast', 'inorm_fast_taken', 'splitk_reduced', 'ring_fixed', 'ring_fixed_taken', 'fd_fixed', 'fd_fixed_taken')
 
 
 def set_option(name, value):
@@ -148,6 +148,8 @@ def _declare(lib):
     _sig(lib, 'savp_conv_special', [P(SavpConvArgs)])
     _sig(lib, 'savp_gate_weights_bytes', [c_i32, c_i32, c_i32], restype=c_i64)
     _sig(lib, 'savp_conv_stats_ok', [P(SavpConvArgs)])
+    _sig(lib, 'savp_fd_fixed_count', [])
+    _sig(lib, 'savp_fd_fixed_probe', [c_i32, c_i32, P(c_i64), c_i32])
     _sig(lib, 'savp_set_option', [ctypes.c_char_p, c_i32])
     _sig(lib, 'savp_get_option', [ctypes.c_char_p, P(c_i32)])
     _sig(lib, 'savp_allreduce_bucket', [c_vp, c_vp, c_vp, c_i64])
