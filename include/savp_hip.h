@@ -277,6 +277,32 @@ int savp_groupnorm_act_fwd(void* stream, const SavpGnormArgs* a);
 int savp_groupnorm_act_bwd(void* stream, const SavpGnormArgs* a);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The site of a normalizer_fn that is the identity (norm_layer = 'none': ops.get_norm_layer('none') = tf.identity, ops.py:1062-1074;
+ * the call sites of the norms above) with its activation (plain_act.hip).  The convolution in front has added its bias into x.
+ * fwd: out[k] = act(x + add[n][c]) for k < nout, routed by out_c0 / out_nc as in SavpInormArgs; bit k of out_bf16: destination k is bf16.
+ * bwd: dx (=|+=) act'(x + add) * sum_k dy[k], the derivative recomputed from x + add (at 0: 0 for ReLU, alpha for LeakyReLU); no output
+ *      is read.  psum (optional) += per sample the column sums of this call's fp32 gradient act' * sum dy, before dx_beta's sum and before
+ *      any rounding to bf16: its rows are the gradient of `add`, its fold over the samples the gradient of the bias in front of the site.
+ *      The sums take no atomics: float64 partial rows in ws, added in a fixed order by a fold launch (one writer per value).
+ * Any HW and C >= 1.  Where C % 4 == 0 and every view has a 16-byte (bf16: 8-byte) aligned base, strides and channel ranges that are
+ * multiples of 4, the kernels move float4 / bf16x4; anything else takes the scalar instantiation.  No allocation, no synchronisation.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct SavpPlainActArgs {
+    int32_t N, HW, C;
+    int32_t act; float alpha;      /* the codes of SavpInormArgs.act */
+    SavpView x;                    /* [N][HW][C] fp32 */
+    const float* add;              /* optional [N][C] fp32, contiguous: added to every pixel of (sample, channel); NULL: nothing is added */
+    int32_t nout; SavpView out[4]; int32_t out_c0[4], out_nc[4]; int32_t out_bf16;
+    int32_t ndy; SavpView dy[4]; int32_t dy_c0[4], dy_nc[4];      /* fp32 */
+    SavpView dx; int32_t dx_beta; int32_t dx_bf16;                 /* dx_beta 0 / 1; a bf16 dx is written only (dx_beta must be 0) */
+    double* psum;                  /* bwd, optional: FLOAT64 accumulator [N][C] (8-byte aligned) */
+    double* ws; int64_t ws_bytes;  /* bwd with psum: scratch of at least N * C * 8 bytes (8-byte aligned, written before it is read); more
+                                      room lets more workgroups share a plane (one partial row of C float64 per workgroup and sample) */
+} SavpPlainActArgs;
+int savp_plain_act_fwd(void* stream, const SavpPlainActArgs* a);
+int savp_plain_act_bwd(void* stream, const SavpPlainActArgs* a);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The pointwise parts of BasicConv2DLSTMCell with separate_norms = True (conv_rnn_norm_layer = 'layer', rnn_ops.py:147-165,
  * savp_model.py:386-390; ln_lstm.hip).  The five layer norms are savp_groupnorm_act_* launches: G = 4 over the gate tensor
  * (input / transform / forget / output, each over (H, W, F)) and G = 1 over the new state.

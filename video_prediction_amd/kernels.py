@@ -700,6 +700,49 @@ def groupnorm_act_bwd(x, gamma, beta, mean, rstd, dys, dx, dgamma, dbeta, groups
     acc.finish()
 
 
+def _plain_act_args(x, add, act, alpha):
+    a = lib.SavpPlainActArgs()
+    a.N, a.HW, a.C = x.shape[0], _hw(x), x.shape[-1]
+    a.act, a.alpha = ACT_IDS[act], float(alpha)
+    a.x = view(x)
+    if add is not None:
+        lib.require_device(add)
+        if tuple(add.shape) != (x.shape[0], x.shape[-1]) or not add.is_contiguous():
+            raise ValueError('add must be a contiguous [N, C] tensor, got %s' % (tuple(add.shape),))
+        a.add = add.data_ptr()
+    return a
+
+
+def plain_act_fwd(x, add, outs, act='relu', alpha=0.0, out_ranges=None):
+    """savp_plain_act_fwd: outs[k] = act(x + add[:, None, None, :]), the site of a normaliser that is the identity (norm_layer = 'none').
+    x [N, ..., C] fp32; add [N, C] fp32 or None (nothing added); outs / out_ranges as in instnorm_act_fwd (fp32 or bf16 views); any C."""
+    a = _plain_act_args(x, add, act, alpha)
+    a.nout = len(outs)
+    _set_views(a.out, outs, any_dtype=True)
+    a.out_bf16 = _bf16_mask(outs)
+    _set_ranges(a.out_c0, a.out_nc, out_ranges)
+    lib.check(lib.get().savp_plain_act_fwd(lib.stream(), ctypes.byref(a)), 'savp_plain_act_fwd')
+
+
+def plain_act_bwd(x, add, dys, dx, dx_beta=0, act='relu', alpha=0.0, dy_ranges=None, psum=None):
+    """savp_plain_act_bwd: dx (=|+=) act'(x + add) * sum(dys); dys / dy_ranges as in instnorm_act_bwd, dx fp32 or bf16.  psum (optional,
+    float64 [N, C]) += per sample the column sums of the fp32 gradient, before any rounding to bf16: the gradient of `add`, and summed
+    over N that of the bias in front of the site.  Deterministic (partial rows in the shared scratch, folded in a fixed order)."""
+    a = _plain_act_args(x, add, act, alpha)
+    a.ndy = len(dys)
+    _set_views(a.dy, dys)
+    _set_ranges(a.dy_c0, a.dy_nc, dy_ranges)
+    a.dx = view(dx, any_dtype=True)
+    a.dx_bf16 = _bf16_mask([dx])
+    a.dx_beta = int(dx_beta)
+    if psum is not None:
+        if psum.dtype != torch.float64 or not psum.is_cuda or not psum.is_contiguous() or tuple(psum.shape) != (x.shape[0], x.shape[-1]):
+            raise ValueError('psum must be a contiguous float64 [N, C] device tensor')
+        ws = scratch(x.device, 2 * x.shape[0] * x.shape[-1])
+        a.psum, a.ws, a.ws_bytes = psum.data_ptr(), ws.data_ptr(), ws.numel() * 4
+    lib.check(lib.get().savp_plain_act_bwd(lib.stream(), ctypes.byref(a)), 'savp_plain_act_bwd')
+
+
 def _lnlstm_args(gn, c_prev, forget_bias):
     a = lib.SavpLnLstmArgs()
     if not gn.is_contiguous() or gn.dtype != torch.float32:

@@ -262,6 +262,15 @@ class SavpGnormArgs(ctypes.Structure):
     _fields_ = [('norm', SavpInormArgs), ('G', c_i32), ('ws_group', c_vp), ('dsum', c_vp)]
 
 
+class SavpPlainActArgs(ctypes.Structure):
+    _fields_ = [
+        ('N', c_i32), ('HW', c_i32), ('C', c_i32), ('act', c_i32), ('alpha', c_f32), ('x', SavpView), ('add', c_vp),
+        ('nout', c_i32), ('out', SavpView * 4), ('out_c0', c_i32 * 4), ('out_nc', c_i32 * 4), ('out_bf16', c_i32),
+        ('ndy', c_i32), ('dy', SavpView * 4), ('dy_c0', c_i32 * 4), ('dy_nc', c_i32 * 4),
+        ('dx', SavpView), ('dx_beta', c_i32), ('dx_bf16', c_i32), ('psum', c_vp), ('ws', c_vp), ('ws_bytes', c_i64),
+    ]
+
+
 class SavpLnLstmArgs(ctypes.Structure):
     _fields_ = [
         ('N', c_i32), ('HW', c_i32), ('F', c_i32), ('forget_bias', c_f32), ('gn', c_vp), ('c_prev', SavpView), ('c_pre', c_vp),
@@ -300,6 +309,8 @@ register('savp_instnorm_act_fwd', [c_vp, ctypes.POINTER(SavpInormArgs)])
 register('savp_instnorm_act_bwd', [c_vp, ctypes.POINTER(SavpInormArgs)])
 register('savp_groupnorm_act_fwd', [c_vp, ctypes.POINTER(SavpGnormArgs)])
 register('savp_groupnorm_act_bwd', [c_vp, ctypes.POINTER(SavpGnormArgs)])
+register('savp_plain_act_fwd', [c_vp, ctypes.POINTER(SavpPlainActArgs)])
+register('savp_plain_act_bwd', [c_vp, ctypes.POINTER(SavpPlainActArgs)])
 register('savp_lnlstm_fwd', [c_vp, ctypes.POINTER(SavpLnLstmArgs), c_i32])
 register('savp_lnlstm_bwd', [c_vp, ctypes.POINTER(SavpLnLstmArgs), c_i32])
 register('savp_convlstm_gates_fwd', [c_vp, ctypes.POINTER(SavpLstmArgs)])

@@ -19,11 +19,12 @@ from . import savp_cell as S      # Act, Norm, ConcatNorm, norm_fwd / norm_bwd a
                                   # so everything of S is read when a cell is built or called, never while this module is imported
 
 
-def cell_class(hp, zw=0, ln_gru=None):
+def cell_class(hp, zw=0, ln_gru=None, norm_none=None):
     """(class, out_norm) of the conv-RNN layers under `hp`.  out_norm: ablation_conv_rnn_norm, the bare cell's output h -- not the state
     handed to the next step -- goes through normalizer_fn (savp_model.py:380-384).  zw: width of the tiled slice [actions | state | z].
-    ln_gru: the opt-in of LayerNormGRU (S.ln_gru_opt_in: None reads SAVP_LN_GRU); without it ('gru', 'layer') is refused."""
-    S.check_norm_layers(hp, ln_gru)
+    ln_gru: the opt-in of LayerNormGRU (S.ln_gru_opt_in: None reads SAVP_LN_GRU); without it ('gru', 'layer') is refused.
+    norm_none: the opt-in of norm_layer='none' (S.norm_none_opt_in: None reads SAVP_NORM_NONE); without it that value is refused."""
+    S.check_norm_layers(hp, ln_gru, zw=zw, norm_none=norm_none)      # (also refuses the untiled latent of a bare cell where nothing cancels it)
     out_norm = bool(hp.ablation_conv_rnn_norm)
     # The cell WITHOUT a normaliser (ConvLSTM, rnn_ops.py:122-125: the gate convolution then has a bias; ConvGRU, :220-223: both
     # convolutions have one): conv_rnn_norm_layer = 'none', or ablation_conv_rnn_norm
@@ -33,11 +34,6 @@ def cell_class(hp, zw=0, ln_gru=None):
     if hp.ablation_rnn:
         return AblationConv, False
     if hp.conv_rnn == 'gru' and bare:
-        if not hp.use_tile_concat and hp.where_add == 'all' and zw:
-            # no norm stands behind the bare cell's two convolutions, so dense(z) (gates/weights, candidate/weights) is NOT cancelled there
-            raise NotImplementedError("conv_rnn='gru' without a cell normaliser (conv_rnn_norm_layer='none' or ablation_conv_rnn_norm) with "
-                                      "use_tile_concat=False, where_add='all' and a latent: the untiled latent of the bare cell is not on "
-                                      "the HIP path")
         return BareGRU, out_norm
     if hp.conv_rnn == 'gru':
         # 'layer' gets here with the opt-in only (check_norm_layers above)
@@ -162,10 +158,15 @@ class AblationConv(ConvRNNCell):
         L['pre2'] = self._act(f, grad_dtype=a16 if f % 8 == 0 else torch.float32)
         L['rconv'] = ConvLayer(gen.store, r + 'conv2d/kernel', r + 'conv2d/bias', 'conv', (5, 5), (1, 1), (2, 2), cx_pad=cin)
         L['n2'] = gen._norm(r, f, bias=r + 'conv2d/bias')
+        hp = gen.hp
+        if gen.nn and not hp.use_tile_concat and hp.where_add == 'all' and gen.zw:
+            gen._untiled(L['n2'], r)          # no norm cancels conv_h<i>/dense(z) either (savp_model.py:475,511)
 
     def forward(self, t, st):
         L = self.L
         self._in_fwd(t, st)
+        if self.gen.nn:
+            L['n2'].add_fwd(t)
         self.gen._conv_norm(('abl', L['idx']), L['rconv'], L['a'].v[t], L['pre2'].v[t], L['n2'], self.gen._out_views(L, t), t)
 
     def backward(self, t, dys):
@@ -177,7 +178,7 @@ class AblationConv(ConvRNNCell):
 
     def backward_weights(self):
         a, p2 = self.L['a'], self.L['pre2']
-        self.L['rconv'].backward_weights(a.flat(a.v), p2.flat(p2.g), feeds_instance_norm=True)
+        self.L['rconv'].backward_weights(a.flat(a.v), p2.flat(p2.g), **self.gen.wkw)
 
 
 class ConvGRU(ConvRNNCell):

@@ -10,6 +10,7 @@ import torch
 from .. import kernels as K
 from .. import lib
 from ..engine import ConvLayer, copy_view, prep_layers
+from .savp_cell import norm_none_opt_in
 from ..variables import NORM_SCOPES, VIDEO_D_LAYERS, video_discriminator_shapes, image_discriminator_shapes
 
 EPS_IN = 1e-6
@@ -22,7 +23,7 @@ class PosteriorEncoder(object):
     prior=True builds prior_fn (:54-85) under its own scope: the convolutional encoder sees only the context_frames-1 context
     pairs, the remaining sequence_length-context_frames feature rows are zeros, and the recurrent tail is always present."""
 
-    def __init__(self, store, hp, image_shape, B, train=True, prefix='generator/encoder/', prior=False, n_actions=0):
+    def __init__(self, store, hp, image_shape, B, train=True, prefix='generator/encoder/', prior=False, n_actions=0, norm_none=None):
         H, W, C = image_shape
         self.hp, self.store = hp, store
         self.T1 = T1 = hp.sequence_length - 1
@@ -37,11 +38,14 @@ class PosteriorEncoder(object):
         M, R = self.M, self.R
         dev = store.device
         self.dev = dev
-        if hp.norm_layer not in NORM_SCOPES:
-            raise NotImplementedError("HIP encoder covers norm_layer in ('instance', 'layer'), not %r" % hp.norm_layer)
+        if hp.norm_layer not in NORM_SCOPES and not (hp.norm_layer == 'none' and norm_none_opt_in(norm_none)):
+            raise NotImplementedError("HIP encoder covers norm_layer in ('instance', 'layer') and, opted in (SAVP_NORM_NONE=1 / "
+                                      "norm_none=True), 'none', not %r" % hp.norm_layer)
         # norm_layer = 'layer': tf.contrib.layers.layer_norm, statistics per sample (csrc/group_norm.hip with one group)
         self.ln = hp.norm_layer == 'layer'
-        ns_ = NORM_SCOPES[hp.norm_layer]
+        # norm_layer = 'none': tf.identity -- layers 2.. are conv + bias -> lrelu on its own kernel (csrc/plain_act.hip), no norm variables
+        self.nn = hp.norm_layer == 'none'
+        ns_ = NORM_SCOPES.get(hp.norm_layer)
         self.recurrent = bool(prior or hp.use_e_rnn)
         if self.recurrent and hp.rnn not in ('lstm', 'gru'):
             raise NotImplementedError(hp.rnn)                                  # savp_model.py:40-41
@@ -62,6 +66,7 @@ class PosteriorEncoder(object):
             if i > 0:
                 L['pre'] = torch.empty(max(M, 1), h, w, cout, device=dev)
                 L['dpre'] = torch.empty(max(M, 1), h, w, cout, device=dev) if train else None
+            if i > 0 and not self.nn:
                 L['gamma'], L['beta'] = store[s + ns_ + 'gamma'], store[s + ns_ + 'beta']
                 L['dgamma'], L['dbeta'] = store.grad64(s + ns_ + 'gamma'), store.grad64(s + ns_ + 'beta')   # float64 accumulators
                 ms = 1 if self.ln else cout
@@ -147,7 +152,9 @@ class PosteriorEncoder(object):
                     L['conv'].forward(L['x'], L['y'], act=lib.ACT_LRELU, alpha=0.2)            # networks.py:18-19
                 else:
                     L['conv'].forward(L['x'], L['pre'])
-                    if self.ln:
+                    if self.nn:
+                        K.plain_act_fwd(L['pre'], None, [L['y']], act='lrelu', alpha=0.2)
+                    elif self.ln:
                         K.groupnorm_act_fwd(L['pre'], L['gamma'], L['beta'], [L['y']], L['mean'], L['rstd'], groups=1, act='lrelu',
                                             alpha=0.2)
                     else:
@@ -209,10 +216,12 @@ class PosteriorEncoder(object):
             K.tile_channels(self.dpooled, lastL['dy'], scale=1.0 / self.hw)
             for i in range(len(self.layers) - 1, -1, -1):
                 L = self.layers[i]
-                if L['normed'] and self.ln:
+                if L['normed'] and self.nn:          # an fp32 dpre: the weight-gradient pass below takes the bias gradient
+                    K.plain_act_bwd(L['pre'], None, [L['dy']], L['dpre'], act='lrelu', alpha=0.2)
+                elif L['normed'] and self.ln:
                     K.groupnorm_act_bwd(L['pre'], L['gamma'], L['beta'], L['mean'], L['rstd'], [L['dy']], L['dpre'],
                                         L['dgamma'], L['dbeta'], groups=1, act='lrelu', alpha=0.2)
-                if L['normed'] and not self.ln:
+                elif L['normed']:
                     K.instnorm_act_bwd(L['pre'], L['gamma'], L['beta'], L['y'], L['mean'], L['rstd'], [L['dy']], L['dpre'],
                                        L['dgamma'], L['dbeta'], act='lrelu', alpha=0.2, eps=EPS_IN)
                 if L['normed']:

@@ -37,12 +37,23 @@ def ln_gru_opt_in(flag=None):
     return bool(flag) if flag is not None else os.environ.get('SAVP_LN_GRU', '0') == '1'
 
 
-def check_norm_layers(hp, ln_gru=None):
-    """The normaliser combinations of the HIP path; anything else raises with the combination named.  ln_gru: see ln_gru_opt_in."""
+def norm_none_opt_in(flag=None):
+    """The opt-in of norm_layer='none' (the generator and the encoders without a normaliser, NoNorm below): the keyword where one was
+    given, else SAVP_NORM_NONE=1 in the environment, read when called.  Without it the value stays refused, as it was."""
+    return bool(flag) if flag is not None else os.environ.get('SAVP_NORM_NONE', '0') == '1'
+
+
+def check_norm_layers(hp, ln_gru=None, zw=None, norm_none=None):
+    """The normaliser combinations of the HIP path; anything else raises with the combination named.  ln_gru: see ln_gru_opt_in;
+    norm_none: see norm_none_opt_in.  zw: width of the slice [actions | state | z] the cell tiles or adds (default: the latent alone, hp.nz)."""
+    zw = hp.nz if zw is None else zw
     if hp.conv_rnn not in ('lstm', 'gru'):
         raise NotImplementedError("conv_rnn=%r" % hp.conv_rnn)
-    if hp.norm_layer not in ('instance', 'layer'):
+    if hp.norm_layer not in ('instance', 'layer', 'none'):
         raise NotImplementedError("norm_layer=%r: the HIP path covers 'instance' and 'layer'" % hp.norm_layer)
+    if hp.norm_layer == 'none' and not norm_none_opt_in(norm_none):
+        raise NotImplementedError("norm_layer='none': the model without a normaliser is opt-in on the HIP path (SAVP_NORM_NONE=1, or the "
+                                  "keyword norm_none=True of the model class / SAVPEngine)")
     if hp.conv_rnn_norm_layer not in ('instance', 'layer', 'none'):
         raise NotImplementedError("conv_rnn_norm_layer=%r: the HIP path covers 'instance', 'layer' and 'none'" % hp.conv_rnn_norm_layer)
     layer = 'layer' in (hp.norm_layer, hp.conv_rnn_norm_layer)
@@ -55,6 +66,21 @@ def check_norm_layers(hp, ln_gru=None):
         # (under ablation_conv_rnn_norm the cell itself has no normaliser and the layer norm sits on the layer's output: covered)
         if hp.conv_rnn == 'gru' and not hp.ablation_conv_rnn_norm and not ln_gru_opt_in(ln_gru):
             raise NotImplementedError("conv_rnn='gru' with conv_rnn_norm_layer='layer': the GRU gate kernels are instance-norm only")
+    # The untiled latent inside a cell WITHOUT a normaliser (conv_rnn_norm_layer='none' or ablation_conv_rnn_norm; both at once is the
+    # selection's own TypeError, conv_rnn_cells.cell_class): no norm stands behind the cell's convolutions, so dense(z) (`weights`,
+    # gates/weights, candidate/weights) is NOT cancelled there, and the cells do not compute it.
+    bare = (hp.conv_rnn_norm_layer == 'none') != bool(hp.ablation_conv_rnn_norm)
+    if bare and not hp.ablation_rnn and not hp.use_tile_concat and hp.where_add == 'all' and zw:
+        if hp.conv_rnn == 'gru':
+            raise NotImplementedError("conv_rnn='gru' without a cell normaliser (conv_rnn_norm_layer='none' or ablation_conv_rnn_norm) with "
+                                      "use_tile_concat=False, where_add='all' and a latent: the untiled latent of the bare cell is not on "
+                                      "the HIP path")
+        if hp.norm_layer == 'none':
+            # with norm_layer='instance' the bare ConvLSTM cell's missing term is the known gap of DESIGN.md section 7, left as it is;
+            # a model without any normaliser must not widen it
+            raise NotImplementedError("norm_layer='none' with conv_rnn='lstm' without a cell normaliser (conv_rnn_norm_layer='none' or "
+                                      "ablation_conv_rnn_norm), use_tile_concat=False, where_add='all' and a latent: the untiled latent of "
+                                      "the bare cell is not on the HIP path")
 
 
 def gru_large_layers(height, width, ngf=32):
@@ -119,9 +145,83 @@ class Norm(object):
         self.rstd = torch.empty(T1, N, C if groups is None else groups, device=device)
 
 
+class _PerStep(object):
+    """What a NoNorm site hands out where a Norm hands out its saved statistics of step t (nrm.mean[t], nrm.rstd[t])."""
+
+    def __init__(self, get):
+        self.get = get
+
+    def __getitem__(self, t):
+        return self.get(t)
+
+
+class NoNorm(object):
+    """A normalizer_fn that is the identity (norm_layer = 'none', ops.py:1062-1074): no gamma / beta, no saved statistics; the site is
+    act(x + add) on csrc/plain_act.hip.  `groups` is 0, not None: everything that assumes an instance norm behind a convolution (the fused
+    conv + norm entries, the statistics and norm-backward epilogues) switches off as it does for a layer norm.
+
+    The bias of the convolution in front is not cancelled by anything.  With an fp32 output gradient that convolution's weight-gradient
+    pass takes the bias gradient as everywhere; with a bf16 one (which takes none) the backward kernel's float64 column sums of its fp32
+    dx supply it: `psum`, folded into the bias variables by finish().
+
+    add: the untiled latent (use_tile_concat=False): dense([actions | state | z]) of every step, [T1, N, C], set by untiled().  Its
+    gradient is the per-(step, sample) rows of the same column sums."""
+    groups = 0
+    gamma = beta = dgamma = dbeta = None
+
+    def __init__(self, store, T1, N, C, device, bias=None, train=True):
+        self.T1, self.N, self.C, self.dev, self.train = T1, N, C, device, train
+        self.dbias = [(store.grad64(bias), 0, C)] if (bias is not None and train) else []      # (float64 accumulator, first channel, count)
+        self.psum = torch.zeros(N, C, device=device, dtype=torch.float64) if train else None      # all steps add to it
+        self.bias_from_psum = False       # a bf16 dx has been written: decided by the first backward call
+        self.add = self.dadd = self.dense = None
+        # the two slots every caller passes on to norm_fwd / norm_bwd: (step t's add term, where step t's column sums go), and nothing
+        self.mean = _PerStep(lambda t: (self.add[t] if self.add is not None else None, self.dadd[t] if self.dadd is not None else self.psum))
+        self.rstd = _PerStep(lambda t: None)
+
+    def untiled(self, dense, zfull):
+        """The site adds dense(zfull) to its input: dense is the bias-free 1x1 ConvLayer of <scope>dense/kernel, zfull [T1, N, zw]."""
+        self.dense, self.zfull = dense, zfull
+        self.add = torch.zeros(self.T1, self.N, self.C, device=self.dev)
+        if self.train:
+            self.dadd = torch.zeros(self.T1, self.N, self.C, device=self.dev, dtype=torch.float64)      # per step: the gradient of add
+            self.dadd32 = torch.empty(self.T1, self.N, self.C, device=self.dev)
+            self.dzfull = torch.empty(self.T1, self.N, zfull.shape[-1], device=self.dev)
+
+    def add_fwd(self, t):
+        if self.dense is not None:
+            self.dense.forward(self.zfull[t], self.add[t])          # the few-row dense kernel, once per step and site
+
+    def finish(self):
+        """After the last step's backward: the bias gradient where the column sums supply it, and with an untiled latent the gradients of
+        dense/kernel (zfull^T . dadd) and of zfull (dadd . W^T, kept for z_gradient).  Clears the accumulators."""
+        acc = self.dadd if self.dadd is not None else self.psum
+        if self.bias_from_psum:
+            tot = acc.sum(0) if acc.dim() == 2 else acc.sum((0, 1))
+            for g64, c0, c in self.dbias:
+                g64.add_(tot[c0:c0 + c])
+        if self.dense is not None:
+            R, zw = self.T1 * self.N, self.zfull.shape[-1]
+            self.dadd32.copy_(self.dadd)
+            d4 = self.dadd32.reshape(R, 1, 1, self.C)
+            self.dense.backward_weights(self.zfull.reshape(R, 1, 1, zw), d4)
+            self.dense.backward_data(d4, self.dzfull.reshape(R, 1, 1, zw), beta=0)
+        if self.bias_from_psum or self.dense is not None:
+            acc.zero_()
+
+    def z_gradient(self, drz, cw):
+        """Adds the latent's share of the untiled term's gradient to drz [T1, N, nz] (the cw conditioning columns in front of it are
+        inputs: skipped)."""
+        if self.dense is not None:
+            drz.add_(self.dzfull[..., cw:])
+
+
 def norm_fwd(nrm, x, outs, mean, rstd, act='relu', eps=EPS_IN, **kw):
     """normalizer_fn + activation of `nrm`'s kind (the instance norm's own epsilon is the caller's; a layer norm always takes 1e-12)."""
-    if nrm.groups is None:
+    if nrm.groups == 0:               # NoNorm: `mean` is (the step's add term, the step's column-sum accumulator)
+        assert kw.pop('stats', None) is None and kw.pop('stats_shift', None) is None, 'no normaliser: nothing takes statistics'
+        K.plain_act_fwd(x, mean[0], outs, act=act, **kw)
+    elif nrm.groups is None:
         K.instnorm_act_fwd(x, nrm.gamma, nrm.beta, outs, mean, rstd, act=act, eps=eps, **kw)
     else:
         K.groupnorm_act_fwd(x, nrm.gamma, nrm.beta, outs, mean, rstd, groups=nrm.groups, act=act, eps=K.EPS_LN, **kw)
@@ -129,7 +229,13 @@ def norm_fwd(nrm, x, outs, mean, rstd, act='relu', eps=EPS_IN, **kw):
 
 def norm_bwd(nrm, x, out0, mean, rstd, dys, dx, dgamma, dbeta, act='relu', eps=EPS_IN, stats=None, **kw):
     """Backward of norm_fwd (out0 is not read)."""
-    if nrm.groups is None:
+    if nrm.groups == 0:               # NoNorm: the column sums are wanted for a bf16 dx (the bias gradient) and for an add term (its gradient)
+        assert stats is None, 'no normaliser: nothing takes backward sums'
+        add, psum = mean
+        if dx.dtype == torch.bfloat16:
+            nrm.bias_from_psum = True
+        K.plain_act_bwd(x, add, dys, dx, act=act, psum=psum if (dx.dtype == torch.bfloat16 or add is not None) else None, **kw)
+    elif nrm.groups is None:
         K.instnorm_act_bwd(x, nrm.gamma, nrm.beta, out0, mean, rstd, dys, dx, dgamma, dbeta, act=act, eps=eps, stats=stats, **kw)
     else:
         assert stats is None, 'the layer norm takes its own backward sums'
@@ -180,6 +286,21 @@ class ConcatNorm(object):
             self.dbias.zero_()
 
 
+class ConcatNoNorm(NoNorm):
+    """ConcatNorm's counterpart for heads without a normaliser: ONE activation launch over the concatenated channels; the column sums of
+    a bf16 gradient go back to each head's own bias variable."""
+
+    def __init__(self, norms, T1, N, device, train=True):
+        super(ConcatNoNorm, self).__init__(None, T1, N, sum(n.C for n in norms), device, train=train)
+        off = 0
+        for n in norms:
+            self.dbias += [(g64, off + c0, c) for g64, c0, c in n.dbias]
+            off += n.C
+
+    def prep(self):
+        pass
+
+
 def check_kernel_size(hp):
     """kernel_size of the CDNA / DNA transformations: sides of at least 1 and at most 49 taps (csrc/cdna_composite.hip keeps 49 per-tap
     accumulators).  Refused when the model is built -- by the engine before it sizes the kernel heads -- not by the first forward."""
@@ -196,7 +317,7 @@ from . import conv_rnn_cells      # noqa: E402  (the cells build on Act, Norm an
 
 
 class SAVPGenerator(object):
-    def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0), pix=0, ln_gru=None):
+    def __init__(self, store, hp, image_shape, N, train=True, prefix='generator/rnn/savp_cell/', cond=(0, 0), pix=0, ln_gru=None, norm_none=None):
         """cond = (n_actions, n_states): widths of inputs['actions'] / inputs['states'] (savp_model.py:411-444): [actions_t | state_t]
         joins the latent in every tile-concatenated slice, the next state is predicted by `state_pred/dense` (:655-658).
         pix = P: designated pixels of inputs['pix_distribs'] (:408-410,598-621,648-653); 0 = the model has no such input and nothing below
@@ -209,10 +330,17 @@ class SAVPGenerator(object):
         dev = store.device
         self.dev = dev
         self._cstats = {}                # head name -> the conv's epilogue supplies the instance norm's statistics (decided at first use)
-        check_norm_layers(hp, ln_gru)
+        norm_none = norm_none_opt_in(norm_none)          # read once: every later check sees the same answer
+        check_norm_layers(hp, ln_gru, norm_none=norm_none)
         # norm_layer = 'layer': every norm_layer site (the ladder's layers, ablation_rnn's conv_h<i>, the 3x3 heads) is a layer norm,
         # variables under <scope>/LayerNorm/ (csrc/group_norm.hip with one group; the heads' merged launch: one group per head)
         self.ln = hp.norm_layer == 'layer'
+        # norm_layer = 'none': every one of those sites is the activation alone (NoNorm, csrc/plain_act.hip), no variables beside the
+        # convolutions' biases; plain_sites: every such site, for finish() after the backward pass
+        self.nn = hp.norm_layer == 'none'
+        self.plain_sites = []
+        # what a convolution in front of a norm_layer site tells its weight-gradient pass about a bf16 output gradient
+        self.wkw = dict(bias_grad_elsewhere=True) if self.nn else dict(feeds_instance_norm=True)
         # downsample_layer / upsample_layer / activation_layer (ops.py:1052-1098; savp_model.py:395-397).  conv2d: the strided SAME
         # convolution, ConvLayer kind 'down'; deconv2d: conv2d_transpose, kind 'deconv'; the _v2 names are aliases (variables.DOWN_SCOPES).
         # elu: the activation code of every norm_layer site of the cell (the ladder, ablation_rnn's conv_h<i>, the 3x3 heads).
@@ -265,9 +393,13 @@ class SAVPGenerator(object):
         # above), and a per-(sample, channel) constant is removed exactly by the norm's mean subtraction: the outputs do not depend on
         # z, the `dense/kernel` / `weights` variables and z itself get zero gradients.  The layers therefore run without z channels and
         # those variables keep their (zero-initialised) gradients; pinned against the oracle, which computes the sums literally.
+        # norm_layer = 'none' is the exception: nothing cancels the sum at a ladder layer's (and ablation_rnn's conv_h<i>) site, so there
+        # dense([actions | state | z]) with <scope>dense/kernel is computed per step and added inside the site's activation kernel
+        # (NoNorm.untiled); its gradients come from that kernel's column sums.  Inside a bare cell the term stays refused (check_norm_layers).
         tile = bool(hp.use_tile_concat)
+        self.untiled = []                    # (NoNorm site, its dense layer): wired to [actions | state | z] once that buffer exists
         # which conv-RNN cell the recurrent layers run (the matrix of DESIGN.md section 1), and whether its output takes a norm of its own
-        cell, out_norm = conv_rnn_cells.cell_class(hp, zw, ln_gru)
+        cell, out_norm = conv_rnn_cells.cell_class(hp, zw, ln_gru, norm_none)
         zr = zw if (hp.where_add == 'all' and tile) else 0              # tiled channels in a conv-RNN's input [x | actions state z | h]
         g = train
         # bf16 storage of tensors whose ONLY readers are convolutions of the bf16 datapath (round 4; the cell input [x | z | h] and the
@@ -289,8 +421,8 @@ class SAVPGenerator(object):
             L = {'f': f, 'rnn': use_rnn, 'idx': i, 'dec': i >= self.ne}
             s = prefix + 'h%d/' % i
             j_dec = i - len(enc_specs)
-            zc = zw if (tile and (hp.where_add == 'all' or (hp.where_add == 'input' and i == 0) or
-                                  (hp.where_add == 'middle' and j_dec == 0))) else 0
+            sel = hp.where_add == 'all' or (hp.where_add == 'input' and i == 0) or (hp.where_add == 'middle' and j_dec == 0)
+            zc = zw if (tile and sel) else 0
             L['zc'], L['zr'] = zc, zr
             if i < self.ne:
                 cx = 2 * C if i == 0 else prev_f
@@ -325,6 +457,8 @@ class SAVPGenerator(object):
             pre16 = f % 8 == 0 and (i < self.ne or L['in'].v.dtype == torch.bfloat16 or not self.act16)
             L['pre'] = Act((T1, N, h_, w_, f), dev, grad=g, grad_dtype=a16 if pre16 else torch.float32)
             L['norm'] = self._norm(s, f, bias=L['conv'].bias_name)
+            if self.nn and not tile and zw and sel:
+                self._untiled(L['norm'], s)
             if use_rnn:
                 L['cell'] = cell(self, L, prefix, out_norm)          # its buffers, ConvLayers and Norms go into L (conv_rnn_cells.py)
             else:
@@ -465,6 +599,8 @@ class SAVPGenerator(object):
                 self.dzW, self.dzb = store.grad64(z + 'kernel'), store.grad64(z + 'bias')      # float64 accumulators (one workgroup per sample adds to them)
                 self.z_gates = torch.empty(T1, N, 4 * nz, device=dev)
                 self.z_cs = torch.empty(T1, N, nz, device=dev)
+        for nrm, dense in self.untiled:
+            nrm.untiled(dense, self.saz if cw else self.rnn_z.v)
         # ---- learn_initial_state (savp_model.py:295-307,344-352): the conv-RNN states and the rnn_z state start from variables
         # `generator/initial_state_<i>/initial_state` (i = position in nest.flatten of {'conv_rnn_states': [...], 'rnn_z_state': ...}: layer
         # order, LSTM tuples as (c, h), the latent cell last), tiled over the batch; both unrolls (N = 2B) share them.  Forward: a broadcast
@@ -501,7 +637,12 @@ class SAVPGenerator(object):
                 tf_convs = [self.tf_out]
             self.nheads = len(parts)
             self.heads_conv = ConcatConv(store, parts, (3, 3), (1, 1), (1, 1))
-            self.heads_norm = ConcatNorm(norms, T1, N, dev)
+            if self.nn:
+                for n in norms:                    # the merged launch stands for them (backward finishes it with heads_norm.finish())
+                    self.plain_sites.remove(n)
+                self.heads_norm = ConcatNoNorm(norms, T1, N, dev, train=g)
+            else:
+                self.heads_norm = ConcatNorm(norms, T1, N, dev)
             self.heads_pre = Act((T1, N, H, W, self.nheads * ngf), dev, grad=g,
                                  grad_dtype=a16 if (self.nheads * ngf) % 8 == 0 else torch.float32)
             head_convs = [self.heads_conv]
@@ -509,7 +650,7 @@ class SAVPGenerator(object):
         #  the weights and finish_weight_grad folds the gradients in this order)
         cell_convs = [L['cell'].convs() for L in self.layers if L['rnn']]
         self.convs = [L['conv'] for L in self.layers] + [c for kind in zip(*cell_convs) for c in kind] + \
-                     ([self.fc_z] if (self.use_rnn_z and self.abl_rnn) else []) + \
+                     ([self.fc_z] if (self.use_rnn_z and self.abl_rnn) else []) + [d for _, d in self.untiled] + \
                      tf_convs + head_convs + ([self.scratch_out] if self.scratch else []) + [self.masks_out]
         # ---- pix_distribs: one launch after the unroll (pix_distribs_forward); the slots in the reference's order (:598-621) ----
         self.P = int(pix)
@@ -652,8 +793,10 @@ class SAVPGenerator(object):
                 # norm is then ONE launch (SAVP_CONV_STATS=0: the norm takes its own statistics)
                 ck = ('cstats', K.PRECISION['value'])          # the answer depends on the datapath in use: decided once per precision
                 if ck not in L:
-                    L[ck] = (CONV_STATS and f <= 256 and (f & (f - 1)) == 0 and L['conv'].stats_ok(L['in'].v[t], L['pre'].v[t]))
+                    L[ck] = (CONV_STATS and not self.nn and f <= 256 and (f & (f - 1)) == 0 and L['conv'].stats_ok(L['in'].v[t], L['pre'].v[t]))
                 st = K.stats_ws(self.dev, N, f) if L[ck] else None
+                if self.nn:
+                    L['norm'].add_fwd(t)          # the untiled latent's dense(z) of this step, where the site takes one
                 if L['rnn']:
                     L['cell'].forward(t, st)
                 else:
@@ -722,9 +865,19 @@ class SAVPGenerator(object):
 
     def _norm(self, scope, c, kind=None, bias=None):
         """The normalizer_fn of `kind` (default: norm_layer) under `scope`: <scope>InstanceNorm/ or <scope>LayerNorm/; bias: the variable
-        name of the bias of the convolution in front of it (a layer norm's backward can supply that bias's gradient)."""
+        name of the bias of the convolution in front of it (a layer norm's backward can supply that bias's gradient, and so can the
+        site of kind 'none', which has no variables of its own)."""
         kind = kind or self.hp.norm_layer
+        if kind == 'none':                # the identity: a parameter-less site (NoNorm)
+            site = NoNorm(self.store, self.T1, self.N, c, self.dev, bias=bias, train=self.train)
+            self.plain_sites.append(site)
+            return site
         return Norm(self.store, scope + NORM_SCOPES[kind], self.T1, self.N, c, self.dev, groups=1 if kind == 'layer' else None, bias=bias)
+
+    def _untiled(self, nrm, scope):
+        """The NoNorm site `nrm` takes the untiled latent: dense([actions | state | z]) with <scope>dense/kernel (no bias,
+        savp_model.py:983-993) added to its input.  The layer is a 1x1 ConvLayer among self.convs; __init__ wires it to the buffer."""
+        self.untiled.append((nrm, ConvLayer(self.store, scope + 'dense/kernel', None, 'conv', (1, 1), (1, 1), (0, 0))))
 
     # ---------------------------------------------------------------------------------------------------------
     def _conv_norm(self, name, conv, x, pre, nrm, outs, t, **kw):
@@ -732,7 +885,8 @@ class SAVPGenerator(object):
         ok = self._cstats.get((name, K.PRECISION['value']))
         if ok is None:
             c = pre.shape[-1]
-            ok = self._cstats[(name, K.PRECISION['value'])] = bool(CONV_STATS and c <= 256 and (c & (c - 1)) == 0 and conv.stats_ok(x, pre))
+            ok = self._cstats[(name, K.PRECISION['value'])] = bool(CONV_STATS and nrm.groups != 0 and c <= 256 and (c & (c - 1)) == 0 and
+                                                                   conv.stats_ok(x, pre))          # (groups 0: no norm, no statistics)
         st = K.stats_ws(self.dev, self.N, pre.shape[-1]) if ok else None
         self._conv_in_act(conv, x, pre, st, nrm, outs, t, **kw)
 
@@ -889,7 +1043,7 @@ class SAVPGenerator(object):
         # ---- weight gradients: one split-K GEMM per layer over all (t, n) ----------------------------------------
         for L in self.layers:
             b, pre = L['in'], L['pre']
-            L['conv'].backward_weights(b.flat(b.v), pre.flat(pre.g), feeds_instance_norm=True)
+            L['conv'].backward_weights(b.flat(b.v), pre.flat(pre.g), **self.wkw)
             if L['rnn']:
                 L['cell'].backward_weights()
         hl = self.h_last
@@ -898,18 +1052,20 @@ class SAVPGenerator(object):
             self.cdna_dense.backward_weights(hs.v.reshape(T1 * N, -1), self.cdna_raw.g.reshape(T1 * N, -1))
         else:
             if not self.merge_heads:
-                self.tf_conv.backward_weights(hl.flat(hl.v), hl.flat(self.tf_pre.g), feeds_instance_norm=True)
+                self.tf_conv.backward_weights(hl.flat(hl.v), hl.flat(self.tf_pre.g), **self.wkw)
             self.tf_out.backward_weights(hl.flat(self.tf_h.v), hl.flat(self.tf_raw.g))
         if self.merge_heads:
-            self.heads_conv.backward_weights(hl.flat(hl.v), hl.flat(self.heads_pre.g), feeds_instance_norm=True)
+            self.heads_conv.backward_weights(hl.flat(hl.v), hl.flat(self.heads_pre.g), **self.wkw)
             self.heads_norm.finish()
         else:
             if self.scratch:
-                self.scratch_conv.backward_weights(hl.flat(hl.v), hl.flat(self.scratch_pre.g), feeds_instance_norm=True)
-            self.masks_conv.backward_weights(hl.flat(hl.v), hl.flat(self.masks_pre.g), feeds_instance_norm=True)
+                self.scratch_conv.backward_weights(hl.flat(hl.v), hl.flat(self.scratch_pre.g), **self.wkw)
+            self.masks_conv.backward_weights(hl.flat(hl.v), hl.flat(self.masks_pre.g), **self.wkw)
         if self.scratch:
             self.scratch_out.backward_weights(hl.flat(self.scratch_h.v), self.dscratch_pre.reshape(T1 * N, self.H, self.W, self.Cs))
         self.masks_out.backward_weights(hl.flat(maskin.v)[..., 0:self.mask_cin], hl.flat(self.logits.g))
+        for site in self.plain_sites:      # norm_layer = 'none': bias gradients from the column sums, the untiled latent's dense layers
+            site.finish()
         for c in self.convs:
             c.finish_weight_grad()
         # ---- state prediction: the state loss's gradient (the caller left it in gen_states.g) through the recurrence ----------
@@ -927,7 +1083,9 @@ class SAVPGenerator(object):
                 K.colsum(b.flat(b.g)[..., L['zoff_in'] + cw:L['zoff_in'] + cw + nz], drz, per_row=True)
             if L['rnn'] and L['zr']:
                 L['cell'].z_gradient(drz)
-        if self.use_rnn_z and self.abl_rnn:               # tanh(dense(z)) backward: d pre = d rnn_z * (1 - rnn_z^2)
+        for nrm, _ in self.untiled:
+            nrm.z_gradient(drz, cw)
+        if self.use_rnn_z and self.abl_rnn:             # tanh(dense(z)) backward: d pre = d rnn_z * (1 - rnn_z^2)
             dpre = self.fcz_pre.g.reshape(T1, N, nz)
             torch.mul(self.rnn_z.v, self.rnn_z.v, out=dpre)
             dpre.neg_().add_(1.0).mul_(drz)

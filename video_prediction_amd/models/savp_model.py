@@ -23,7 +23,7 @@ from ..engine import ParamStore, copy_view, add_views
 from .base_model import VideoPredictionModel, learning_rate, kl_weight
 from .hparam_defaults import savp_defaults, SAVP_DEPRECATED_KEYS
 from .networks import PosteriorEncoder, SNDiscriminator
-from .savp_cell import SAVPGenerator, check_kernel_size, check_norm_layers, ln_gru_opt_in
+from .savp_cell import SAVPGenerator, check_kernel_size, check_norm_layers, ln_gru_opt_in, norm_none_opt_in
 
 
 def _image_shape(images):
@@ -159,7 +159,7 @@ class SAVPEngine(object):
     UNSUPPORTED_WEIGHTS = ('vgg_cdist_weight', 'feature_l2_weight', 'ae_l2_weight')
 
     def __init__(self, hp, image_shape, batch_size, mode='train', values=None, seed=4, device='cuda:0', base_seed=0, rank=0,
-                 cond=(0, 0), lpips_weights=None, pix_distribs=0, store=None, guard=None, ln_gru=None):
+                 cond=(0, 0), lpips_weights=None, pix_distribs=0, store=None, guard=None, ln_gru=None, norm_none=None):
         """store: the ParamStore of another engine to look the variables up in instead of creating them (a mode='test' engine only: the
         long_sequence_length model of scripts/train.py); every name this engine needs must be there with its shape.
         pix_distribs = P: the number of designated pixels of inputs['pix_distribs'] [B, T, H, W, P] (savp_model.py:252-255,408-410,598-621,
@@ -172,10 +172,13 @@ class SAVPEngine(object):
         SAVP_GUARD environment variable, '1' = on; off otherwise).  mode='train' only: an inference engine has no gradient and ignores it.
         Off, the step has no buffer, launch or graph node for it.  See guard_enabled() and _guarded_adam().
         ln_gru: the opt-in of the layer-norm ConvGRU cell, conv_rnn='gru' with conv_rnn_norm_layer='layer' (default: the SAVP_LN_GRU
-        environment variable, '1' = on); without it that combination is refused and nothing differs for any other model."""
+        environment variable, '1' = on); without it that combination is refused and nothing differs for any other model.
+        norm_none: the opt-in of norm_layer='none', the generator and the encoders without a normaliser (default: the SAVP_NORM_NONE
+        environment variable, '1' = on); without it that value is refused and nothing differs for any other model."""
         self.hp, self.mode, self.B = hp, mode, batch_size
         self.ln_gru = ln_gru_opt_in(ln_gru)
-        check_norm_layers(hp, self.ln_gru)     # before anything is allocated (the generator checks again)
+        self.norm_none = norm_none_opt_in(norm_none)
+        check_norm_layers(hp, self.ln_gru, norm_none=self.norm_none)     # before anything is allocated (the generator checks again)
         bad = [k for k in self.UNSUPPORTED_WEIGHTS if getattr(hp, k, 0)]
         if bad and mode == 'train':
             raise NotImplementedError('loss weights not covered by the HIP path: %s' % ', '.join(bad))
@@ -214,11 +217,11 @@ class SAVPEngine(object):
         self.P = int(pix_distribs or 0)
         if self.P < 0:
             raise ValueError('pix_distribs = %r: the number of designated pixels' % (pix_distribs,))
-        self.gen = SAVPGenerator(store, hp, image_shape, N, train=self.train, cond=self.cond, pix=self.P, ln_gru=self.ln_gru)
+        self.gen = SAVPGenerator(store, hp, image_shape, N, train=self.train, cond=self.cond, pix=self.P, ln_gru=self.ln_gru, norm_none=self.norm_none)
         # designated-pixel distributions, staged time-major beside the images (sliced to T1 like every input: savp_model.py:690-691)
         self.pix_tm = torch.empty(self.T1, B, H, W, self.P, device=self.device) if self.P else None
         self.pix_n = (torch.empty(self.T1, N, H, W, self.P, device=self.device) if self.nz else self.pix_tm) if self.P else None
-        self.enc = PosteriorEncoder(store, hp, image_shape, B, train=self.train, n_actions=self.na) if self.nz else None
+        self.enc = PosteriorEncoder(store, hp, image_shape, B, train=self.train, n_actions=self.na, norm_none=self.norm_none) if self.nz else None
         # conditioning inputs, time-major; both unrolls (N = 2B: posterior half, prior half) see the same actions / states
         self.actions_tm = torch.zeros(self.T1, B, self.na, device=self.device) if self.na else None
         self.actions_n = (torch.zeros(self.T1, N, self.na, device=self.device) if self.nz else self.actions_tm) if self.na else None
@@ -237,7 +240,7 @@ class SAVPEngine(object):
         # learned prior (prior_fn, savp_model.py:54-85,717-721): its own encoder + recurrent tail under scope generator/prior
         self.learn_prior = bool(self.nz and hp.learn_prior)
         self.prior = (PosteriorEncoder(store, hp, image_shape, B, train=self.train, prefix='generator/prior/', prior=True,
-                                       n_actions=self.na)
+                                       n_actions=self.na, norm_none=self.norm_none)
                       if self.learn_prior else None)
         # (discriminator, loss weight, loss-name infix, operates on the posterior ('_enc') unroll?, clip index keys)
         self.discs = []
@@ -1165,7 +1168,7 @@ class _ParallelPriorEval(object):
         T, T1, nz = eng.T, eng.T1, eng.nz
         self.F = F = T - hp.context_frames
         self.c1 = hp.context_frames - 1
-        self.gen = SAVPGenerator(eng.net_store, hp, eng.image_shape, N, train=False, cond=eng.cond, ln_gru=eng.ln_gru)
+        self.gen = SAVPGenerator(eng.net_store, hp, eng.image_shape, N, train=False, cond=eng.cond, ln_gru=eng.ln_gru, norm_none=eng.norm_none)
         self.images = torch.empty(T, N, H, W, C, device=dev)
         self.zs = torch.zeros(T1, N, nz, device=dev)
         gt = torch.zeros(T1, N, dtype=torch.int32)
@@ -1520,6 +1523,8 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         guard = kwargs.pop('guard', None)
         # opt-in of the layer-norm ConvGRU cell (ln_gru=True, or SAVP_LN_GRU=1); without it conv_rnn='gru' + conv_rnn_norm_layer='layer' is refused
         self.ln_gru = ln_gru_opt_in(kwargs.pop('ln_gru', None))
+        # opt-in of norm_layer='none' (norm_none=True, or SAVP_NORM_NONE=1); without it that value is refused
+        self.norm_none = norm_none_opt_in(kwargs.pop('norm_none', None))
         super(SAVPVideoPredictionModel, self).__init__(generator_fn, discriminator_fn, *args, **kwargs)
         if self.mode != 'train':
             self.discriminator_fn = None
@@ -1562,7 +1567,7 @@ class SAVPVideoPredictionModel(VideoPredictionModel):
         B = images.shape[0]
         self.engine = SAVPEngine(self.hparams, tuple(images.shape[2:]), B, mode=self.mode, values=values, seed=seed,
                                  device=device, cond=cond_of(inputs), lpips_weights=self.lpips_weights, pix_distribs=P, store=store,
-                                 guard=self.guard, ln_gru=self.ln_gru)
+                                 guard=self.guard, ln_gru=self.ln_gru, norm_none=self.norm_none)
         self.saveable_variables = self.engine.store.names()
         self.post_init_ops = []
         self.outputs = {}
