@@ -693,7 +693,7 @@ int savp_dna_apply_multi_bwd(void* stream, const SavpDnaMultiArgs* a);
  *  output stage: pre [N,HW,F]  -> c = tanh(IN(pre)); h' = u*h + (1-u)*c written to nout destinations
  *  backward    : out_bwd gives dpre(F), du and dh = u*dh' (overwrites); gates_bwd gives dpre(2F) and dh += d(rh)*r (accumulates)
  * Three families share SavpGruArgs: these four (one workgroup holds a plane in registers: HW <= 1024, SAVP_EINVAL above), the bare
- * cell's pointwise savp_convgru_plain_* (any plane) and the chunked two-pass savp_convgru_large_* of gru_large.hip (instance norm,
+ * cell's pointwise savp_convgru_plain_* (any plane) and the chunked two-pass savp_convgru_large_* of gru_two_pass.hip (instance norm,
  * any plane; the generator uses them for layers whose plane exceeds 1024 pixels).
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct SavpGruArgs {
@@ -732,7 +732,7 @@ int savp_convgru_plain_gates_fwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_plain_out_fwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_plain_out_bwd(void* stream, const SavpGruArgs* a);
 int savp_convgru_plain_gates_bwd(void* stream, const SavpGruArgs* a);
-/* gru_large.hip: the four INSTANCE-NORM blocks above (same mathematics, same fields of SavpGruArgs, same overwrite / accumulate
+/* gru_two_pass.hip: the four INSTANCE-NORM blocks above (same mathematics, same fields of SavpGruArgs, same overwrite / accumulate
  * contract of dh) for planes of ANY size HW >= 1; savp_convgru_{gates,out}_{fwd,bwd} keep their HW <= 1024 limit.  Each block is two
  * launches over chunks of pixels: a sums pass (forward: shifted sum / sum of squares of `pre`; backward: sum dz and sum dz*xhat, which
  * are dbeta and dgamma) that STORES per-chunk float64 partials to `ws`, and an apply pass that folds them in chunk order and writes
@@ -755,10 +755,10 @@ int savp_convgru_large_gates_fwd(void* stream, const SavpGruLargeArgs* a);
 int savp_convgru_large_out_fwd(void* stream, const SavpGruLargeArgs* a);
 int savp_convgru_large_out_bwd(void* stream, const SavpGruLargeArgs* a);
 int savp_convgru_large_gates_bwd(void* stream, const SavpGruLargeArgs* a);
-/* ln_gru.hip: the four blocks with LAYER norms inside the cell (rnn_ops.py:234-267 with separate_norms = True, i.e. conv_rnn_norm_layer =
+/* gru_two_pass.hip: the four blocks with LAYER norms inside the cell (rnn_ops.py:234-267 with separate_norms = True, i.e. conv_rnn_norm_layer =
  * 'layer'): r = sigmoid(LN(pre[..., :F])), u = sigmoid(LN(pre[..., F:])), c = tanh(LN(pre)) with LN = tf.contrib.layers.layer_norm --
  * statistics per sample over (HW, F) of that tensor, biased variance, eps as given (1e-12).  Same fields of SavpGruLargeArgs, same
- * overwrite / accumulate contract of dh, planes of ANY size HW >= 1, and the two-pass structure of gru_large.hip (per-chunk float64
+ * overwrite / accumulate contract of dh, planes of ANY size HW >= 1, and the two-pass structure of savp_convgru_large_* (per-chunk float64
  * partials STORED to `ws`, folded in a fixed order; no fp32 atomics, nothing to clear, nothing allocated: legal in a captured graph).
  * What differs:
  *  gamma, beta : [2F] = (reset | update) for the gates stage, [F] for the output stage

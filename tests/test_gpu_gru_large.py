@@ -1,4 +1,4 @@
-"""The instance-norm Conv2DGRUCell on planes above 1024 pixels (csrc/gru_large.hip, K.convgru_large_*): the four chunked two-pass gate
+"""The instance-norm Conv2DGRUCell on planes above 1024 pixels (csrc/gru_two_pass.hip, K.convgru_large_*): the four chunked two-pass gate
 blocks against fp64 autograd on tests/aux_refs.gru_gates / gru_out (rows and bounds of tests/gpu_checks_aux.check_convgru_blocks, plus the
 saved statistics, guard bands and bit-reproducibility), what they refuse, and a 64 x 80 generator -- conv-RNN planes of 32 x 40 in two
 layers, 16 x 20 and 8 x 10 in the other three -- against the fp64 oracle: the generator forward on both datapaths.

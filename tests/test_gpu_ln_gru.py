@@ -1,4 +1,4 @@
-"""The layer-norm Conv2DGRUCell (conv_rnn='gru' with conv_rnn_norm_layer='layer', opt-in; csrc/ln_gru.hip, K.convgru_ln_*): the four chunked
+"""The layer-norm Conv2DGRUCell (conv_rnn='gru' with conv_rnn_norm_layer='layer', opt-in; csrc/gru_two_pass.hip, K.convgru_ln_*): the four chunked
 two-pass gate blocks against fp64 autograd (every view a strided slice of a guarded buffer, the workspace NaN-filled, the bounds TOL_OP and
 AUX.TOL_GRAD as tests/test_gpu_gru_large.py uses them), what they refuse, and the opt-in model against the fp64 oracle extended by
 tests/oracle_ln_gru.py with the helpers and bounds of tests/gpu_model_checks.py."""

@@ -1,4 +1,4 @@
-"""Host side of the large-plane instance-norm ConvGRU blocks (csrc/gru_large.hip), no GPU: the chunk and workspace arithmetic kernels.py
+"""Host side of the large-plane instance-norm ConvGRU blocks (csrc/gru_two_pass.hip), no GPU: the chunk and workspace arithmetic kernels.py
 restates against the library's own, the ctypes mirror of SavpGruLargeArgs against the header, the entries' refusals that need no launch,
 and the generator's per-layer choice between the one-workgroup and the chunked blocks as a function of the frame size."""
 import ctypes

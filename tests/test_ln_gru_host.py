@@ -1,4 +1,4 @@
-"""Host side of the layer-norm ConvGRU cell (conv_rnn='gru' with conv_rnn_norm_layer='layer', opt-in; csrc/ln_gru.hip), no GPU: the
+"""Host side of the layer-norm ConvGRU cell (conv_rnn='gru' with conv_rnn_norm_layer='layer', opt-in; csrc/gru_two_pass.hip), no GPU: the
 refusal without the opt-in, the selection with it, the variable table, the fp64 oracle cell of tests/oracle_ln_gru.py against a plain-loop
 numpy restatement, and the workspace arithmetic and launch-free refusals of the new entries."""
 import ctypes

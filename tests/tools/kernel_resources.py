@@ -75,7 +75,7 @@ def main():
     for r in recs:
         regs = -(-(r['vgpr'] + r['agpr']) // 8) * 8
         waves = min(8, 512 // max(regs, 1))
-        short = re.sub(r'\(.*$', '', r['name'].replace('void ', ''))
+        short = re.sub(r'\(.*$', '', r['name'].replace('void ', '').replace('(anonymous namespace)::', ''))
         print('%5d %5d %5d %7d %7d %8d %8d %5d %6d  %s' % (r['vgpr'], r['agpr'], r['sgpr'], r['sspill'], r['vspill'], r['lds'], r['scratch'], r['wg'], waves, short))
 
 

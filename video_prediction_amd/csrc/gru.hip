@@ -7,19 +7,12 @@
 //                                                                         conv sees [x, h, r*h], rnn_ops.py:242,258)
 //   output stage: c = tanh(IN_F(conv5x5([x, h, r*h]))) ; h' = u*h + (1-u)*c
 // The same blocks of the cell without a normaliser are pointwise and stand at the end of the file (savp_convgru_plain_*).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "savp_hip.h"
+// The parameter struct, its host fill and the device helpers are those of every GRU block family (gru_blocks.h); planes above
+// MAXPPT * NT pixels run on gru_two_pass.hip.
+#include "gru_blocks.h"
 
-#define NT 256
-#define MAXPPT 4
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? SAVP_OK : SAVP_ELAUNCH)
+#define MAXPPT 4                      // pixels of the plane a thread holds in registers
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 template <int NV>
 __device__ __forceinline__ void block_sum(float (&v)[NV], float* sh) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -33,33 +26,6 @@ __device__ __forceinline__ void block_sum(float (&v)[NV], float* sh) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] = sh[i] + sh[NV + i] + sh[2 * NV + i] + sh[3 * NV + i];
 }
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_(float x) {
-    float e = __expf(-2.f * fabsf(x));
-    return copysignf((1.f - e) / (1.f + e), x);
-}
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-struct GruP {
-    int N, HW, F;
-    float eps;
-    const float* pre;                                    // gates stage: [N,HW,2F]; output stage: [N,HW,F]
-    const float* h; long long h_sn, h_sp;                // h_prev view (never null: zero state is a zero buffer)
-    const float *gamma, *beta;
-    float *mean, *rstd;                                  // [N,2F] / [N,F]
-    float* u;                                            // [N,HW,F] contiguous (gates: written, output: read)
-    float* rh; long long rh_sn, rh_sp;                   // gates fwd: r*h destination view
-    int nout; float* out[4]; long long o_sn[4], o_sp[4]; // output fwd: h' destinations
-    const float* hnew; long long hn_sn, hn_sp;           // output bwd: saved h' (any destination)
-    // backward
-    int ndy; const float* dy[4]; long long dy_sn[4], dy_sp[4];
-    float* dpre;                                         // [N,HW,F] or [N,HW,2F]
-    float* du;                                           // output bwd: d u (post-sigmoid) [N,HW,F]; gates bwd reads it
-    float* dh; long long dh_sn, dh_sp;                   // gradient of h_prev: out bwd overwrites it (u*dh'), gates bwd adds d(rh)*r
-    const float* drh; long long drh_sn, drh_sp;          // gates bwd: gradient of the r*h slot
-    double *dgamma, *dbeta;            // float64 accumulators (savp_hip.h SavpGruArgs)
-};
 
 // ---- gates stage forward: IN over 2F channels (this WG: channels c0..c0+3 of r and of u) ---------------------------
 __global__ __launch_bounds__(NT) void gru_gates_fwd_kernel(GruP p) {
@@ -308,32 +274,12 @@ __global__ __launch_bounds__(NT) void gru_gates_bwd_kernel(GruP p) {
     }
 }
 
-static int fill_gru(GruP& p, const SavpGruArgs* a, bool any_plane = false) {
-    if (!a || a->F % 4 || a->HW < 1 || (!any_plane && a->HW > MAXPPT * NT) || !a->pre || !a->h.p) return SAVP_EINVAL;
-    if (a->nout < 0 || a->nout > 4 || a->ndy < 0 || a->ndy > 4) return SAVP_EINVAL;
-    p.N = a->N; p.HW = a->HW; p.F = a->F; p.eps = a->eps;
-    p.pre = a->pre;
-    p.h = (const float*)a->h.p; p.h_sn = a->h.sn; p.h_sp = a->h.sp;
-    p.gamma = a->gamma; p.beta = a->beta; p.mean = a->mean; p.rstd = a->rstd;
-    p.u = a->u;
-    p.rh = (float*)a->rh.p; p.rh_sn = a->rh.sn; p.rh_sp = a->rh.sp;
-    p.nout = a->nout;
-    for (int i = 0; i < a->nout; ++i) { p.out[i] = (float*)a->out[i].p; p.o_sn[i] = a->out[i].sn; p.o_sp[i] = a->out[i].sp; }
-    p.ndy = a->ndy;
-    for (int i = 0; i < a->ndy; ++i) { p.dy[i] = (const float*)a->dy[i].p; p.dy_sn[i] = a->dy[i].sn; p.dy_sp[i] = a->dy[i].sp; }
-    p.dpre = a->dpre; p.du = a->du;
-    p.dh = (float*)a->dh.p; p.dh_sn = a->dh.sn; p.dh_sp = a->dh.sp;
-    p.drh = (const float*)a->drh.p; p.drh_sn = a->drh.sn; p.drh_sp = a->drh.sp;
-    p.dgamma = a->dgamma; p.dbeta = a->dbeta;
-    return SAVP_OK;
-}
-
 #define GRU_ENTRY(name, kernel, cond)                                                                              \
     extern "C" int name(void* stream, const SavpGruArgs* a) {                                                      \
         GruP p;                                                                                                     \
-        int rc = fill_gru(p, a);                                                                                    \
+        int rc = fill_gru(p, a, GRU_SMALL);                                                                         \
         if (rc) return rc;                                                                                          \
-        if (!(cond)) return SAVP_EINVAL;                                                                            \
+        if (a->HW > MAXPPT * NT || !(cond)) return SAVP_EINVAL;                                                     \
         hipLaunchKernelGGL(kernel, dim3(a->N * (a->F / 4)), dim3(NT), 0, (hipStream_t)stream, p);                   \
         return LAUNCH_OK();                                                                                         \
     }
@@ -450,18 +396,12 @@ __global__ __launch_bounds__(NT) void gru_plain_gates_bwd_kernel(GruP p) {
     }
 }
 
-// a float4 at every (sample, pixel, 4-channel group) of a view needs a 16-byte base and strides that are multiples of 4 floats
-static bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
-static bool view_ok(const void* q, long long sn, long long sp) { return q && al16(q) && sn % 4 == 0 && sp % 4 == 0; }
-
 #define GRU_PLAIN_ENTRY(name, kernel, cond)                                                                        \
     extern "C" int name(void* stream, const SavpGruArgs* a) {                                                      \
         GruP p;                                                                                                     \
-        int rc = fill_gru(p, a, true);                                                                              \
+        int rc = fill_gru(p, a, GRU_PLAIN);                                                                         \
         if (rc) return rc;                                                                                          \
-        if (a->N < 1 || !al16(p.pre) || !view_ok(p.h, p.h_sn, p.h_sp) || !(cond)) return SAVP_EINVAL;              \
-        for (int k = 0; k < p.nout; ++k) if (!view_ok(p.out[k], p.o_sn[k], p.o_sp[k])) return SAVP_EINVAL;         \
-        for (int k = 0; k < p.ndy; ++k) if (!view_ok(p.dy[k], p.dy_sn[k], p.dy_sp[k])) return SAVP_EINVAL;         \
+        if (!(cond)) return SAVP_EINVAL;                                                                            \
         const long long total = (long long)a->N * a->HW * (a->F / 4);                                              \
         long long blocks = (total + NT - 1) / NT;                                                                   \
         if (blocks > PLAIN_MAX_BLOCKS) blocks = PLAIN_MAX_BLOCKS;                                                   \

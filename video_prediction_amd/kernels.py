@@ -1693,89 +1693,149 @@ def dna_apply_multi_bwd(imgs, raw, kern, dout, draw, dimgs, kh, kw, K_, dimg_bet
 # ---------------------------------------------------------------------------------------------------------------
 # ConvGRU gate blocks
 # ---------------------------------------------------------------------------------------------------------------
-def _gru_args(pre, h, gamma, beta, mean, rstd, F, eps):
-    a = lib.SavpGruArgs()
+# Four families of the same four blocks (gates_fwd, out_fwd, out_bwd, gates_bwd; csrc/gru_blocks.h), by the norm inside the cell and the
+# plane size.  The blocks are written once below (_gru_*); a family is its entries' prefix after savp_convgru_ and which of the optional
+# arguments it passes: norm = (gamma, beta, mean, rstd) and, backward, dparams = (dgamma, dbeta); ws (SavpGruLargeArgs); eps.
+#   ''       instance norm, one workgroup per plane: HW <= GRU_SMALL_MAX_HW (csrc/gru.hip)
+#   'plain_' no normaliser: `pre` holds the convolution's output with its bias; pointwise, any plane size (csrc/gru.hip)
+#   'large_' instance norm, any plane size: chunked sums pass + apply pass, per-chunk float64 partials in `ws` (csrc/gru_two_pass.hip)
+#   'ln_'    LAYER norms (conv_rnn_norm_layer = 'layer'), the same two passes: gamma / beta are [2F] = (reset | update) or [F], mean / rstd
+#            are [N, 2] or [N, 1], dgamma / dbeta stay per channel
+_NO_WS = object()          # the family takes no workspace (ws = None is a two-pass call without one, which the entry refuses)
+
+
+def _gru_args(pre, h, norm, F, eps, ws):
+    """The structure an entry takes, with what every block sets; its SavpGruArgs is .g where the family takes a workspace."""
+    if ws is _NO_WS:
+        whole = a = lib.SavpGruArgs()
+    else:
+        whole = lib.SavpGruLargeArgs()
+        a = whole.g
+        if ws is not None:
+            lib.require_stats(ws)
+            whole.ws, whole.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     a.N, a.HW, a.F, a.eps = pre.shape[0], _hw(pre), F, float(eps)
     assert pre.is_contiguous()
     a.pre = _p(pre)
     a.h = view(h)
-    a.gamma, a.beta, a.mean, a.rstd = _p(gamma), _p(beta), _p(mean), _p(rstd)
-    return a
+    if norm is not None:
+        a.gamma, a.beta, a.mean, a.rstd = _p(norm[0]), _p(norm[1]), _p(norm[2]), _p(norm[3])
+    return whole, a
 
 
-def convgru_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, eps=1e-6):
-    a = _gru_args(pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
+def _gru_gates_fwd(entry, pre, h, norm, u, rh, ws=_NO_WS, eps=0.0):
+    whole, a = _gru_args(pre, h, norm, pre.shape[-1] // 2, eps, ws)
     a.u, a.rh = _p(u), view(rh)
-    lib.check(_L().savp_convgru_gates_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_gates_fwd')
+    lib.check(getattr(_L(), entry)(lib.stream(), ctypes.byref(whole)), entry)
+
+
+def _gru_out_fwd(entry, pre, h, norm, u, outs, ws=_NO_WS, eps=0.0):
+    whole, a = _gru_args(pre, h, norm, pre.shape[-1], eps, ws)
+    a.u = _p(u)
+    a.nout = len(outs)
+    _set_views(a.out, outs)
+    lib.check(getattr(_L(), entry)(lib.stream(), ctypes.byref(whole)), entry)
+
+
+def _gru_bwd(entry, whole, a, dparams):
+    """Launches a backward block; dparams = (dgamma, dbeta) of the family's norm, None without one."""
+    if dparams is None:
+        lib.check(getattr(_L(), entry)(lib.stream(), ctypes.byref(whole)), entry)
+        return
+    acc = _Acc64(dparams[0], dparams[1])
+    a.dgamma, a.dbeta = acc.addr(0), acc.addr(1)
+    lib.check(getattr(_L(), entry)(lib.stream(), ctypes.byref(whole)), entry)
+    acc.finish()
+
+
+def _gru_out_bwd(entry, pre, h, norm, u, dys, dpre, du, dh, dparams=None, ws=_NO_WS, eps=0.0):
+    whole, a = _gru_args(pre, h, norm, pre.shape[-1], eps, ws)
+    a.u = _p(u)
+    a.ndy = len(dys)
+    _set_views(a.dy, dys)
+    a.dpre, a.du, a.dh = _p(dpre), _p(du), view(dh)
+    _gru_bwd(entry, whole, a, dparams)
+
+
+def _gru_gates_bwd(entry, pre, h, norm, du, drh, dpre, dh, dparams=None, ws=_NO_WS, eps=0.0):
+    whole, a = _gru_args(pre, h, norm, pre.shape[-1] // 2, eps, ws)
+    a.du, a.drh, a.dpre, a.dh = _p(du), view(drh), _p(dpre), view(dh)
+    _gru_bwd(entry, whole, a, dparams)
+
+
+# the sixteen public names
+def convgru_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, eps=1e-6):
+    _gru_gates_fwd('savp_convgru_gates_fwd', pre, h, (gamma, beta, mean, rstd), u, rh, _NO_WS, eps)
 
 
 def convgru_out_fwd(pre, h, gamma, beta, mean, rstd, u, outs, eps=1e-6):
-    a = _gru_args(pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
-    a.u = _p(u)
-    a.nout = len(outs)
-    _set_views(a.out, outs)
-    lib.check(_L().savp_convgru_out_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_out_fwd')
+    _gru_out_fwd('savp_convgru_out_fwd', pre, h, (gamma, beta, mean, rstd), u, outs, _NO_WS, eps)
 
 
 def convgru_out_bwd(pre, h, gamma, beta, mean, rstd, u, dys, dpre, du, dh, dgamma, dbeta, eps=1e-6):
-    a = _gru_args(pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
-    a.u = _p(u)
-    a.ndy = len(dys)
-    _set_views(a.dy, dys)
-    a.dpre, a.du, a.dh = _p(dpre), _p(du), view(dh)
-    acc = _Acc64(dgamma, dbeta)
-    a.dgamma, a.dbeta = acc.addr(0), acc.addr(1)
-    lib.check(_L().savp_convgru_out_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_out_bwd')
-    acc.finish()
+    _gru_out_bwd('savp_convgru_out_bwd', pre, h, (gamma, beta, mean, rstd), u, dys, dpre, du, dh, (dgamma, dbeta), _NO_WS, eps)
 
 
 def convgru_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma, dbeta, eps=1e-6):
-    a = _gru_args(pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
-    a.du, a.drh, a.dpre, a.dh = _p(du), view(drh), _p(dpre), view(dh)
-    acc = _Acc64(dgamma, dbeta)
-    a.dgamma, a.dbeta = acc.addr(0), acc.addr(1)
-    lib.check(_L().savp_convgru_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_gates_bwd')
-    acc.finish()
+    _gru_gates_bwd('savp_convgru_gates_bwd', pre, h, (gamma, beta, mean, rstd), du, drh, dpre, dh, (dgamma, dbeta), _NO_WS, eps)
 
 
-# the cell without a normaliser: `pre` holds the convolution's output with its bias; pointwise, any plane size
 def convgru_plain_gates_fwd(pre, h, u, rh):
-    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1] // 2, 0.0)
-    a.u, a.rh = _p(u), view(rh)
-    lib.check(_L().savp_convgru_plain_gates_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_gates_fwd')
+    _gru_gates_fwd('savp_convgru_plain_gates_fwd', pre, h, None, u, rh)
 
 
 def convgru_plain_out_fwd(pre, h, u, outs):
-    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1], 0.0)
-    a.u = _p(u)
-    a.nout = len(outs)
-    _set_views(a.out, outs)
-    lib.check(_L().savp_convgru_plain_out_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_out_fwd')
+    _gru_out_fwd('savp_convgru_plain_out_fwd', pre, h, None, u, outs)
 
 
 def convgru_plain_out_bwd(pre, h, u, dys, dpre, du, dh):
-    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1], 0.0)
-    a.u = _p(u)
-    a.ndy = len(dys)
-    _set_views(a.dy, dys)
-    a.dpre, a.du, a.dh = _p(dpre), _p(du), view(dh)
-    lib.check(_L().savp_convgru_plain_out_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_out_bwd')
+    _gru_out_bwd('savp_convgru_plain_out_bwd', pre, h, None, u, dys, dpre, du, dh)
 
 
 def convgru_plain_gates_bwd(pre, h, du, drh, dpre, dh):
-    a = _gru_args(pre, h, None, None, None, None, pre.shape[-1] // 2, 0.0)
-    a.du, a.drh, a.dpre, a.dh = _p(du), view(drh), _p(dpre), view(dh)
-    lib.check(_L().savp_convgru_plain_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_plain_gates_bwd')
+    _gru_gates_bwd('savp_convgru_plain_gates_bwd', pre, h, None, du, drh, dpre, dh)
 
 
-# the instance-norm cell on planes of any size (csrc/gru_large.hip): chunked sums pass + apply pass, per-chunk float64 partials in `ws`
-GRU_SMALL_MAX_HW = 1024           # MAXPPT x NT of csrc/gru.hip: convgru_* above refuse more, convgru_large_* take any plane
-GRU_LARGE_MAX_CHUNKS = 64         # GL_MAX_CHUNKS
-GRU_LARGE_PARTIALS = 4            # GL_K: float64 partials per channel of F and chunk
+def convgru_large_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, ws, eps=1e-6):
+    _gru_gates_fwd('savp_convgru_large_gates_fwd', pre, h, (gamma, beta, mean, rstd), u, rh, ws, eps)
+
+
+def convgru_large_out_fwd(pre, h, gamma, beta, mean, rstd, u, outs, ws, eps=1e-6):
+    _gru_out_fwd('savp_convgru_large_out_fwd', pre, h, (gamma, beta, mean, rstd), u, outs, ws, eps)
+
+
+def convgru_large_out_bwd(pre, h, gamma, beta, mean, rstd, u, dys, dpre, du, dh, dgamma, dbeta, ws, eps=1e-6):
+    _gru_out_bwd('savp_convgru_large_out_bwd', pre, h, (gamma, beta, mean, rstd), u, dys, dpre, du, dh, (dgamma, dbeta), ws, eps)
+
+
+def convgru_large_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma, dbeta, ws, eps=1e-6):
+    _gru_gates_bwd('savp_convgru_large_gates_bwd', pre, h, (gamma, beta, mean, rstd), du, drh, dpre, dh, (dgamma, dbeta), ws, eps)
+
+
+def convgru_ln_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, ws, eps=EPS_LN):
+    _gru_gates_fwd('savp_convgru_ln_gates_fwd', pre, h, (gamma, beta, mean, rstd), u, rh, ws, eps)
+
+
+def convgru_ln_out_fwd(pre, h, gamma, beta, mean, rstd, u, outs, ws, eps=EPS_LN):
+    _gru_out_fwd('savp_convgru_ln_out_fwd', pre, h, (gamma, beta, mean, rstd), u, outs, ws, eps)
+
+
+def convgru_ln_out_bwd(pre, h, gamma, beta, mean, rstd, u, dys, dpre, du, dh, dgamma, dbeta, ws, eps=EPS_LN):
+    _gru_out_bwd('savp_convgru_ln_out_bwd', pre, h, (gamma, beta, mean, rstd), u, dys, dpre, du, dh, (dgamma, dbeta), ws, eps)
+
+
+def convgru_ln_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma, dbeta, ws, eps=EPS_LN):
+    _gru_gates_bwd('savp_convgru_ln_gates_bwd', pre, h, (gamma, beta, mean, rstd), du, drh, dpre, dh, (dgamma, dbeta), ws, eps)
+
+
+GRU_SMALL_MAX_HW = 1024           # MAXPPT x NT of csrc/gru.hip: convgru_* refuse more, convgru_large_* and convgru_ln_* take any plane
+GRU_LARGE_MAX_CHUNKS = 64         # G2_MAX_CHUNKS of csrc/gru_two_pass.hip
+GRU_LARGE_PARTIALS = 4            # G2_K: float64 partials per channel of F and chunk
+LN_GRU_MAX_F = 1024               # GRU_LN_MAX_F of csrc/gru_blocks.h
 
 
 def convgru_large_chunk(N, HW):
-    """Pixels per workgroup of the convgru_large_* launchers (savp_convgru_large_chunk restated, so that it is known without the library):
+    """Pixels per workgroup of the two-pass launchers (savp_convgru_large_chunk restated, so that it is known without the library):
     about 512 workgroups per launch, between 32 and 256 pixels, and at most GRU_LARGE_MAX_CHUNKS chunks per plane."""
     if N < 1 or HW < 1:
         return 0
@@ -1786,7 +1846,7 @@ def convgru_large_chunk(N, HW):
 
 
 def convgru_large_ws_bytes(N, HW, F):
-    """Bytes of the float64 workspace [N, chunks, 4, F] one convgru_large_* call needs (savp_convgru_large_ws_bytes restated)."""
+    """Bytes of the float64 workspace [N, chunks, 4, F] one two-pass call needs (savp_convgru_large_ws_bytes restated)."""
     c = convgru_large_chunk(N, HW)
     if not c or F < 1:
         return 0
@@ -1794,107 +1854,12 @@ def convgru_large_ws_bytes(N, HW, F):
 
 
 def convgru_large_ws(device, N, HW, F):
-    """A workspace for the convgru_large_* calls of one layer: allocated once by the caller, its contents never matter between calls."""
+    """A workspace for the two-pass calls of one layer: allocated once by the caller, its contents never matter between calls."""
     return torch.empty(convgru_large_ws_bytes(N, HW, F) // 8, dtype=torch.float64, device=device)
 
 
-def _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, F, eps):
-    a = lib.SavpGruLargeArgs()
-    a.g = _gru_args(pre, h, gamma, beta, mean, rstd, F, eps)
-    if ws is not None:
-        lib.require_stats(ws)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    return a
-
-
-def convgru_large_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, ws, eps=1e-6):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
-    a.g.u, a.g.rh = _p(u), view(rh)
-    lib.check(_L().savp_convgru_large_gates_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_gates_fwd')
-
-
-def convgru_large_out_fwd(pre, h, gamma, beta, mean, rstd, u, outs, ws, eps=1e-6):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
-    a.g.u = _p(u)
-    a.g.nout = len(outs)
-    _set_views(a.g.out, outs)
-    lib.check(_L().savp_convgru_large_out_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_out_fwd')
-
-
-def convgru_large_out_bwd(pre, h, gamma, beta, mean, rstd, u, dys, dpre, du, dh, dgamma, dbeta, ws, eps=1e-6):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
-    a.g.u = _p(u)
-    a.g.ndy = len(dys)
-    _set_views(a.g.dy, dys)
-    a.g.dpre, a.g.du, a.g.dh = _p(dpre), _p(du), view(dh)
-    acc = _Acc64(dgamma, dbeta)
-    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
-    lib.check(_L().savp_convgru_large_out_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_out_bwd')
-    acc.finish()
-
-
-def convgru_large_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma, dbeta, ws, eps=1e-6):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
-    a.g.du, a.g.drh, a.g.dpre, a.g.dh = _p(du), view(drh), _p(dpre), view(dh)
-    acc = _Acc64(dgamma, dbeta)
-    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
-    lib.check(_L().savp_convgru_large_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_large_gates_bwd')
-    acc.finish()
-
-
-# the cell with LAYER norms inside (conv_rnn_norm_layer = 'layer', csrc/ln_gru.hip): the same two-pass blocks for a plane of any size;
-# gamma / beta are [2F] = (reset | update) or [F], mean / rstd are [N, 2] or [N, 1], dgamma / dbeta stay per channel
-LN_GRU_MAX_F = 1024               # LG_MAX_F
-
-
-def convgru_ln_chunk(N, HW):
-    """Pixels per workgroup of the convgru_ln_* launchers (savp_convgru_ln_chunk restated): the rule of convgru_large_chunk."""
-    return convgru_large_chunk(N, HW)
-
-
-def convgru_ln_ws_bytes(N, HW, F):
-    """Bytes of the float64 workspace [N, chunks, 4, F] one convgru_ln_* call needs (savp_convgru_ln_ws_bytes restated)."""
-    return convgru_large_ws_bytes(N, HW, F)
-
-
-def convgru_ln_ws(device, N, HW, F):
-    """A workspace for the convgru_ln_* calls of one layer: allocated once by the caller, its contents never matter between calls."""
-    return torch.empty(convgru_ln_ws_bytes(N, HW, F) // 8, dtype=torch.float64, device=device)
-
-
-def convgru_ln_gates_fwd(pre, h, gamma, beta, mean, rstd, u, rh, ws, eps=EPS_LN):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
-    a.g.u, a.g.rh = _p(u), view(rh)
-    lib.check(_L().savp_convgru_ln_gates_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_gates_fwd')
-
-
-def convgru_ln_out_fwd(pre, h, gamma, beta, mean, rstd, u, outs, ws, eps=EPS_LN):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
-    a.g.u = _p(u)
-    a.g.nout = len(outs)
-    _set_views(a.g.out, outs)
-    lib.check(_L().savp_convgru_ln_out_fwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_out_fwd')
-
-
-def convgru_ln_out_bwd(pre, h, gamma, beta, mean, rstd, u, dys, dpre, du, dh, dgamma, dbeta, ws, eps=EPS_LN):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1], eps)
-    a.g.u = _p(u)
-    a.g.ndy = len(dys)
-    _set_views(a.g.dy, dys)
-    a.g.dpre, a.g.du, a.g.dh = _p(dpre), _p(du), view(dh)
-    acc = _Acc64(dgamma, dbeta)
-    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
-    lib.check(_L().savp_convgru_ln_out_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_out_bwd')
-    acc.finish()
-
-
-def convgru_ln_gates_bwd(pre, h, gamma, beta, mean, rstd, du, drh, dpre, dh, dgamma, dbeta, ws, eps=EPS_LN):
-    a = _gru_large_args(ws, pre, h, gamma, beta, mean, rstd, pre.shape[-1] // 2, eps)
-    a.g.du, a.g.drh, a.g.dpre, a.g.dh = _p(du), view(drh), _p(dpre), view(dh)
-    acc = _Acc64(dgamma, dbeta)
-    a.g.dgamma, a.g.dbeta = acc.addr(0), acc.addr(1)
-    lib.check(_L().savp_convgru_ln_gates_bwd(lib.stream(), ctypes.byref(a)), 'savp_convgru_ln_gates_bwd')
-    acc.finish()
+# the layer-norm blocks take the same chunks and the same workspace
+convgru_ln_chunk, convgru_ln_ws_bytes, convgru_ln_ws = convgru_large_chunk, convgru_large_ws_bytes, convgru_large_ws
 
 
 GAN_TYPES = {'LSGAN': 0, 'GAN': 1, 'SNGAN': 2}

@@ -497,20 +497,14 @@ class SavpGruArgs(ctypes.Structure):
                 ('dh', SavpView), ('drh', SavpView), ('dgamma', c_vp), ('dbeta', c_vp)]
 
 
-for _n in ('savp_convgru_gates_fwd', 'savp_convgru_out_fwd', 'savp_convgru_out_bwd', 'savp_convgru_gates_bwd',
-           'savp_convgru_plain_gates_fwd', 'savp_convgru_plain_out_fwd', 'savp_convgru_plain_out_bwd', 'savp_convgru_plain_gates_bwd'):
-    register(_n, [c_vp, ctypes.POINTER(SavpGruArgs)])
-
-
 class SavpGruLargeArgs(ctypes.Structure):
     _fields_ = [('g', SavpGruArgs), ('ws', c_vp), ('ws_bytes', c_i64)]
 
 
-for _n in ('savp_convgru_large_gates_fwd', 'savp_convgru_large_out_fwd', 'savp_convgru_large_out_bwd', 'savp_convgru_large_gates_bwd'):
-    register(_n, [c_vp, ctypes.POINTER(SavpGruLargeArgs)])
-# the layer-norm cell's blocks (csrc/ln_gru.hip) take the same structure: mean / rstd are [N][G] there
-for _n in ('savp_convgru_ln_gates_fwd', 'savp_convgru_ln_out_fwd', 'savp_convgru_ln_out_bwd', 'savp_convgru_ln_gates_bwd'):
-    register(_n, [c_vp, ctypes.POINTER(SavpGruLargeArgs)])
+# the four blocks of every family (csrc/gru_blocks.h); the two-pass families take the workspace (the layer norm's mean / rstd are [N][G])
+for _fam, _args in (('', SavpGruArgs), ('plain_', SavpGruArgs), ('large_', SavpGruLargeArgs), ('ln_', SavpGruLargeArgs)):
+    for _n in ('gates_fwd', 'out_fwd', 'out_bwd', 'gates_bwd'):
+        register('savp_convgru_' + _fam + _n, [c_vp, ctypes.POINTER(_args)])
 register('savp_gan_loss', [c_vp, c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_i32])
 register('savp_fold_f64', [c_vp, c_vp, c_i64, c_vp, c_vp])
 register('savp_tv_loss', [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp])

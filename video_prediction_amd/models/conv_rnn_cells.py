@@ -183,8 +183,11 @@ class AblationConv(ConvRNNCell):
 
 class ConvGRU(ConvRNNCell):
     """Conv2DGRUCell (rnn_ops.py:174-267): a = [x | z | h_prev | r*h_prev]; the gates conv reads the first f+zc+f channels of the same
-    buffer (a channel-slice view), the candidate conv reads all of it.  The subclasses supply the four gate blocks."""
+    buffer (a channel-slice view), the candidate conv reads all of it.  The four gate blocks are one call each of a wrapper in K: a
+    subclass names them in `blocks` (a table like GRU_BLOCKS, resolved when called) and sets self.norms = (the norm of the gates, the norm
+    of the candidate, the workspace arguments, eps) -- (None, None, (), None) without a normaliser."""
     bias = False           # without a normaliser the two convolutions carry a bias (rnn_ops.py:220-223)
+    blocks = None
 
     def __init__(self, gen, L, prefix, out_norm=False):
         super(ConvGRU, self).__init__(gen, L, prefix, out_norm)
@@ -239,16 +242,42 @@ class ConvGRU(ConvRNNCell):
         self.L['rconv'].backward_weights(a.flat(a.v)[..., 0:self.L['cin1']], gt.flat(gt.g))
         self.L['cconv'].backward_weights(a.flat(a.v), cd.flat(cd.g))
 
+    # ---- the four gate blocks ----
+    def _block(self, which, t, norm, pre, hprev, *operands):
+        """K.<blocks[which]>(pre, h, [gamma, beta, mean, rstd,] operands, [dgamma, dbeta,] [workspace,] [eps])."""
+        ws, eps = self.norms[2:]
+        if norm is None:
+            args = operands
+        else:
+            args = (norm.gamma, norm.beta, norm.mean[t], norm.rstd[t]) + operands + \
+                   ((norm.dgamma, norm.dbeta) if which.endswith('bwd') else ()) + ws + (eps,)
+        getattr(K, self.blocks[which])(pre, hprev, *args)
+        if 'gru_large_calls' in self.L:
+            self.L['gru_large_calls'] += 1
 
-# the gate blocks of the instance-norm GRU, by plane size: names of wrappers in K, resolved when called
-GRU_BLOCKS = dict(gates_fwd='convgru_gates_fwd', out_fwd='convgru_out_fwd', out_bwd='convgru_out_bwd', gates_bwd='convgru_gates_bwd')
-GRU_LARGE_BLOCKS = dict(gates_fwd='convgru_large_gates_fwd', out_fwd='convgru_large_out_fwd', out_bwd='convgru_large_out_bwd',
-                        gates_bwd='convgru_large_gates_bwd')
+    def gates_fwd(self, t, hprev, rh):
+        self._block('gates_fwd', t, self.norms[0], self.L['gates'].v[t], hprev, self.L['u'][t], rh)
+
+    def out_fwd(self, t, hprev, hdst):
+        self._block('out_fwd', t, self.norms[1], self.L['cand'].v[t], hprev, self.L['u'][t], hdst)
+
+    def out_bwd(self, t, hprev, dys):
+        L = self.L
+        self._block('out_bwd', t, self.norms[1], L['cand'].v[t], hprev, L['u'][t], dys, L['cand'].g[t], L['du'], L['dh_tmp'])
+
+    def gates_bwd(self, t, hprev, drh, dhprev):
+        L = self.L
+        self._block('gates_bwd', t, self.norms[0], L['gates'].v[t], hprev, L['du'], drh, L['gates'].g[t], dhprev)
+
+
+# the gate blocks by family: names of wrappers in K, resolved when called
+GRU_BLOCKS, GRU_LARGE_BLOCKS, LN_GRU_BLOCKS, BARE_GRU_BLOCKS = (
+    {b: 'convgru_' + fam + b for b in ('gates_fwd', 'out_fwd', 'out_bwd', 'gates_bwd')} for fam in ('', 'large_', 'ln_', 'plain_'))
 
 
 class InstanceNormGRU(ConvGRU):
     """The GRU cell with its instance norms (gates/reset_update, candidate/state) inside the gate blocks.  A plane the one-workgroup
-    blocks (csrc/gru.hip) hold runs on them; a larger one (gru_large_layers) on the chunked two-pass blocks (csrc/gru_large.hip), which
+    blocks (csrc/gru.hip) hold runs on them; a larger one (gru_large_layers) on the chunked two-pass blocks (csrc/gru_two_pass.hip), which
     take a per-layer workspace as one more argument.  The choice is made here, once per layer."""
 
     def __init__(self, gen, L, prefix, out_norm=False):
@@ -264,41 +293,20 @@ class InstanceNormGRU(ConvGRU):
             raise NotImplementedError("conv_rnn='gru' with its instance norm on a conv-RNN plane of %dx%d = %d pixels (layer h%d, above "
                                       "%d): mode='train' is not offered at this frame size yet, generation and evaluation are "
                                       "(profiles/gru_large.md)" % (h_, w_, h_ * w_, L['idx'], K.GRU_SMALL_MAX_HW))
-        self.blocks, self.ws = GRU_BLOCKS, ()
+        self.blocks, ws = GRU_BLOCKS, ()
         if L['gru_large']:
             L['gru_ws'] = K.convgru_large_ws(gen.dev, gen.N, h_ * w_, f)
-            L['gru_large_calls'] = 0          # counts the launches of the large blocks (tests read it)
-            self.blocks, self.ws = GRU_LARGE_BLOCKS, (L['gru_ws'],)
-
-    def _block(self, which, *args):
-        getattr(K, self.blocks[which])(*args, *self.ws, eps=S.EPS_IN)
-        if self.ws:
-            self.L['gru_large_calls'] += 1
-
-    def gates_fwd(self, t, hprev, rh):
-        L, n1 = self.L, self.L['n1']
-        self._block('gates_fwd', L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['u'][t], rh)
-
-    def out_fwd(self, t, hprev, hdst):
-        L, n2 = self.L, self.L['n2']
-        self._block('out_fwd', L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], hdst)
-
-    def out_bwd(self, t, hprev, dys):
-        L, n2 = self.L, self.L['n2']
-        self._block('out_bwd', L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], dys, L['cand'].g[t], L['du'],
-                    L['dh_tmp'], n2.dgamma, n2.dbeta)
-
-    def gates_bwd(self, t, hprev, drh, dhprev):
-        L, n1 = self.L, self.L['n1']
-        self._block('gates_bwd', L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'], drh, L['gates'].g[t], dhprev,
-                    n1.dgamma, n1.dbeta)
+            L['gru_large_calls'] = 0          # counts the calls of the large blocks (tests read it)
+            self.blocks, ws = GRU_LARGE_BLOCKS, (L['gru_ws'],)
+        self.norms = (L['n1'], L['n2'], ws, S.EPS_IN)
 
 
 class LayerNormGRU(ConvGRU):
     """conv_rnn_norm_layer = 'layer' inside the GRU cell (separate_norms, rnn_ops.py:234-267): the gates convolution (no bias), a layer
     norm each for reset and update (one G = 2 block, parameters gathered per step), the candidate convolution, a layer norm of the
-    candidate, h'.  The norms run inside the chunked two-pass gate blocks of csrc/ln_gru.hip: one code path for every plane size, a
+    candidate, h'.  The norms run inside the chunked two-pass gate blocks of csrc/gru_two_pass.hip: one code path for every plane size, a
     per-layer workspace created here, no normalised tensor stored.  Opt-in (S.ln_gru_opt_in)."""
+    blocks = LN_GRU_BLOCKS
 
     def __init__(self, gen, L, prefix, out_norm=False):
         super(LayerNormGRU, self).__init__(gen, L, prefix)
@@ -313,27 +321,10 @@ class LayerNormGRU(ConvGRU):
                                  for nm in ('reset', 'update')], gen.T1, gen.N, gen.dev)
         L['nC'] = S.Norm(gen.store, r + 'candidate/state/', gen.T1, gen.N, f, gen.dev, groups=1)
         L['ln_gru_ws'] = K.convgru_ln_ws(gen.dev, gen.N, h_ * w_, f)
+        self.norms = (L['gn2'], L['nC'], (L['ln_gru_ws'],), K.EPS_LN)
 
     def prep(self):
         self.L['gn2'].prep()
-
-    def gates_fwd(self, t, hprev, rh):
-        L, n1 = self.L, self.L['gn2']
-        K.convgru_ln_gates_fwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['u'][t], rh, L['ln_gru_ws'], eps=K.EPS_LN)
-
-    def out_fwd(self, t, hprev, hdst):
-        L, n2 = self.L, self.L['nC']
-        K.convgru_ln_out_fwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], hdst, L['ln_gru_ws'], eps=K.EPS_LN)
-
-    def out_bwd(self, t, hprev, dys):
-        L, n2 = self.L, self.L['nC']
-        K.convgru_ln_out_bwd(L['cand'].v[t], hprev, n2.gamma, n2.beta, n2.mean[t], n2.rstd[t], L['u'][t], dys, L['cand'].g[t], L['du'],
-                             L['dh_tmp'], n2.dgamma, n2.dbeta, L['ln_gru_ws'], eps=K.EPS_LN)
-
-    def gates_bwd(self, t, hprev, drh, dhprev):
-        L, n1 = self.L, self.L['gn2']
-        K.convgru_ln_gates_bwd(L['gates'].v[t], hprev, n1.gamma, n1.beta, n1.mean[t], n1.rstd[t], L['du'], drh, L['gates'].g[t], dhprev,
-                               n1.dgamma, n1.dbeta, L['ln_gru_ws'], eps=K.EPS_LN)
 
     def backward_weights(self):
         super(LayerNormGRU, self).backward_weights()
@@ -343,23 +334,12 @@ class LayerNormGRU(ConvGRU):
 class BareGRU(ConvGRU):
     """The GRU cell without a normaliser: conv + bias, pointwise gate blocks of any plane size (csrc/gru.hip)."""
     bias = True
+    blocks = BARE_GRU_BLOCKS
 
     def __init__(self, gen, L, prefix, out_norm=False):
         super(BareGRU, self).__init__(gen, L, prefix, out_norm)
         self._make_out_norm(prefix + 'gru_h%d/' % L['idx'])
-
-    def gates_fwd(self, t, hprev, rh):
-        K.convgru_plain_gates_fwd(self.L['gates'].v[t], hprev, self.L['u'][t], rh)
-
-    def out_fwd(self, t, hprev, hdst):
-        K.convgru_plain_out_fwd(self.L['cand'].v[t], hprev, self.L['u'][t], hdst)
-
-    def out_bwd(self, t, hprev, dys):
-        L = self.L
-        K.convgru_plain_out_bwd(L['cand'].v[t], hprev, L['u'][t], dys, L['cand'].g[t], L['du'], L['dh_tmp'])
-
-    def gates_bwd(self, t, hprev, drh, dhprev):
-        K.convgru_plain_gates_bwd(self.L['gates'].v[t], hprev, self.L['du'], drh, self.L['gates'].g[t], dhprev)
+        self.norms = (None, None, (), None)
 
 
 class ConvLSTM(ConvRNNCell):

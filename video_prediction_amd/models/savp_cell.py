@@ -85,7 +85,7 @@ def check_norm_layers(hp, ln_gru=None, zw=None, norm_none=None):
 
 def gru_large_layers(height, width, ngf=32):
     """Indices into the encoder + decoder layer table of the conv-RNN layers whose plane exceeds the 1024 pixels the one-workgroup
-    ConvGRU gate blocks (csrc/gru.hip) hold: with the instance-norm GRU cell those layers run on K.convgru_large_* (csrc/gru_large.hip),
+    ConvGRU gate blocks (csrc/gru.hip) hold: with the instance-norm GRU cell those layers run on K.convgru_large_* (csrc/gru_two_pass.hip),
     the others on K.convgru_*.  A function of the frame size alone."""
     enc, dec = layer_specs(ngf, height, width)
     out, h, w = [], height, width
